@@ -10,14 +10,18 @@ Weights are seeded synthetic (no checkpoint can be fetched); arithmetic in bf16
 with f32 accumulation / residual adds / LayerNorm statistics / softmax; the residual
 stream stored in f16 (the library default for bf16 engines; `--residual f32` for f32).
 
-Also reported: texts/s for configs[2] (text tower, batch 1024 x 77 tokens);
+A plain run sets up, warms up, times the K steps, writes the last step's embeddings if
+`--dump-outputs DIR` is given (DIR/vision_embeddings.npy, float32) and prints the headline line.
+
+With `--full`, measured after the timed steps and reported in the same line: texts/s for configs[2]
+(text tower, batch 1024 x 77 tokens);
 roofline of the dominant kernel (the trunk GEMM site with the most time per step) from HIP
 events on the launch stream;
 end-to-end legs through the host-buffer entry points (PCIe included; N = 1);
 CPU baseline = the fp32 torch CPU port of the same graphs (oracle/torch_cpu.py) on a bounded
 sample of the same inputs on rank 0, which also checks the GPU rows (cosine).
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  N > 1: one rank per GPU.  Started without a
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR].  N > 1: one rank per GPU.  Started without a
 torch.distributed launcher (no WORLD_SIZE in the environment), bench.py starts the N ranks itself --
 `python -m torch.distributed.run --nproc-per-node N` as a child process, before anything touches the GPU
 -- and exits with its status; rank 0 prints the JSON line.  Under a launcher, WORLD_SIZE must equal
@@ -476,8 +480,18 @@ def main():
     ap.add_argument("--gather", action="store_true",
                     help="N = 1: run the data-parallel path anyway (gloo control plane, the engine's RCCL "
                          "communicator, gathered entry points) -- a one-GPU rehearsal of N > 1")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every side measurement (GEMM-site roofline passes, "
+                         "windows, fp8, text leg, end-to-end legs, CPU baseline; --breakdown); without it the run "
+                         "only sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/vision_embeddings.npy: the float32 "
+                         "[gpus * 256, 512] embedding matrix the timed entry point fills (same arguments, same "
+                         "seeded inputs and weights: comparable across builds)")
     ap.add_argument("--plumbing-check", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.breakdown and not args.full:
+        ap.error("--breakdown is a side measurement: pass --full with it")
 
     w = resolve_world(args.gpus, os.environ)
     if isinstance(w, int):
@@ -563,6 +577,47 @@ def main():
     images = world * B_VISION * args.steps
     value = images / dt
     ms_per_step = dt * 1e3 / args.steps
+    whole_tflops = vit_flops(B_VISION, executed=True) * args.steps / dt / 1e12 / 1.0
+    if args.dump_outputs and rank == 0:
+        # the timed entry point's output after its last step (synchronized by timed()): this rank's
+        # [256, 512] rows, or with the all-gather every rank's
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "vision_embeddings.npy"),
+                (out_full if dp else out).cpu().numpy().astype(np.float32, copy=False))
+    # The headline: everything the timed steps alone give (a plain run prints this and ends).
+    head = {
+        "metric": "images/sec embedding, ViT-B/32-224 vision tower, batch 256 per GPU",
+        "value": round(value, 1),
+        "unit": "images/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": args.dtype,
+        "data": "synthetic (seeded u8 images normalised with OpenAI mean/std; seeded weights)",
+        "config": {"workload": "BASELINE.json configs[1]: ViT-B/32-224 VisionEmbedder, batch 256 "
+                               "synthetic 224x224 per GPU, device-resident input",
+                   "global_batch": world * B_VISION, "seq_len": 50,
+                   "parallelism": f"dp{world}, {dev_lanes.value} concurrent sub-batch lane(s)/GPU (committed MI355X tile table)" + (" + the engine's RCCL all-gather (ncclAllGather in the C ABI) of the [B,512] embeddings on every rank" if dp else "")},
+        "gemm_tiles": gemm_tiles,
+        "gemm_tiles_env": ",".join(str(t) for t in tiles),
+        "lanes_env": dev_lanes.value,
+        "whole_forward_mfma_tflops_per_gpu": round(whole_tflops, 1),
+        "whole_forward_frac_of_peak": round(whole_tflops / PEAK_BF16_TFLOPS, 4),
+        "last_layer_pruned": PRUNE_LAST,
+        "residual_stream": x_store,
+        "ln_fold": ln_fold,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        ve.close()
+        if dp:
+            dist.destroy_process_group()
+        return 0
     # Per-launch kernel time of the four trunk GEMM sites: a separate pass with HIP events at the
     # kernel boundaries of every launch.  Profiling runs the engine's two lanes (half-batch
     # sub-forwards) one after the other instead of concurrently, so it is kept out of the timed
@@ -610,7 +665,6 @@ def main():
     dom = max(sites, key=lambda k: sites[k]["us_per_step"])
     dom_epi = SITE_EPI[dom].format(x=x_store, ln="LayerNorm folded, " if ln_fold else "")
     fc_rows_per_launch = sites["c_fc"]["rows_per_launch"]
-    whole_tflops = vit_flops(B_VISION, executed=True) * args.steps / dt / 1e12 / 1.0
 
     # Per-kernel-class time per step (lanes serialized, no graph): where the step goes.
     breakdown = None
@@ -744,22 +798,7 @@ def main():
                             if not fp8 else (None, None))
     if rank == 0:
         line = {
-            "metric": "images/sec embedding, ViT-B/32-224 vision tower, batch 256 per GPU",
-            "value": round(value, 1),
-            "unit": "images/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": args.dtype,
-            "data": "synthetic (seeded u8 images normalised with OpenAI mean/std; seeded weights)",
-            "config": {"workload": "BASELINE.json configs[1]: ViT-B/32-224 VisionEmbedder, batch 256 "
-                                   "synthetic 224x224 per GPU, device-resident input",
-                       "global_batch": world * B_VISION, "seq_len": 50,
-                       "parallelism": f"dp{world}, {dev_lanes.value} concurrent sub-batch lane(s)/GPU (committed MI355X tile table)" + (" + the engine's RCCL all-gather (ncclAllGather in the C ABI) of the [B,512] embeddings on every rank" if dp else "")},
+            **head,
             "roofline": {"bound": "mfma",
                          "kernel": f"{dom} GEMM ({sites[dom]['shape']}, {dom_epi}, tile {sites[dom]['tile']}): the "
                                    f"site with the most GEMM time per step",
@@ -778,14 +817,6 @@ def main():
                                            "(lanes serialized); us_per_step sums the site's launches; concurrent: the "
                                            "same with both lanes running, cu_us_per_step = its launches' time x "
                                            "min(blocks, CUs) / CUs (the CU time the site takes per step)"),
-            "gemm_tiles": gemm_tiles,
-            "gemm_tiles_env": ",".join(str(t) for t in tiles),
-            "lanes_env": dev_lanes.value,
-            "whole_forward_mfma_tflops_per_gpu": round(whole_tflops, 1),
-            "whole_forward_frac_of_peak": round(whole_tflops / PEAK_BF16_TFLOPS, 4),
-            "last_layer_pruned": PRUNE_LAST,
-            "residual_stream": x_store,
-            "ln_fold": ln_fold,
             "windows": windows,
             "sclk_mhz": windows["sclk_mhz_median"] if windows else None,
             **({"breakdown_serialized": breakdown} if breakdown is not None else {}),

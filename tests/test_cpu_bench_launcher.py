@@ -43,6 +43,17 @@ def test_bench_gpus_1_runs_in_process():
     assert r.stdout.strip() == ""
 
 
+def test_bench_side_measurements_need_full():
+    """A plain run only times its steps: --breakdown (a pass of its own) is refused without --full,
+    before anything touches the GPU; --full and --dump-outputs are documented options."""
+    r = _run(["--gpus", "1", "--breakdown"])
+    assert r.returncode == 2
+    assert "--full" in r.stderr
+    r = _run(["--help"])
+    assert r.returncode == 0
+    assert "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+
+
 def test_resolve_world():
     sys.path.insert(0, ROOT)
     import importlib.util

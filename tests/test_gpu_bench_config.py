@@ -96,6 +96,40 @@ def test_bench_text_config_matches_oracle(bench_mod):
     te.close()
 
 
+def test_bench_plain_run_and_dump(bench_mod, tmp_path, monkeypatch, capsys):
+    """A plain run (no --full) times exactly --steps steps and prints only the headline line;
+    --dump-outputs writes the last step's [256, 512] float32 embeddings, which are the bits a fresh
+    engine computes from the bench's seeded inputs (so two builds can be compared row for row)."""
+    import json
+    import torch
+    from open_clip_inference import _lib
+    from open_clip_inference.engine import Engine
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1",
+                                     "--dump-outputs", str(tmp_path / "dump")])
+    assert bench_mod.main() == 0
+    lines = [json.loads(l) for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = lines[0]
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert line["unit"] == "images/s" and line["higher_is_better"] is True and line["dtype"] == "bf16"
+    assert line["ms_per_step"] > 0
+    # value and ms_per_step are the same measurement (both rounded in the line)
+    assert abs(line["value"] * line["ms_per_step"] / 1e3 / bench_mod.B_VISION - 1) < 1e-3
+    for side in ("roofline", "gemm_sites", "windows", "text", "end_to_end", "fp8", "cpu_baseline"):
+        assert side not in line
+    got = np.load(tmp_path / "dump" / "vision_embeddings.npy")
+    assert got.dtype == np.float32 and got.shape == (bench_mod.B_VISION, 512)
+    assert np.all(np.abs(np.linalg.norm(got, axis=1) - 1) < 1e-5)
+    dev = torch.device("cuda", 0)
+    ve = Engine(bench_mod.make_model_dir(), _lib.TOWER_VISION, [0], "bf16", bench_mod.B_VISION)
+    px, _ = bench_mod.synth_inputs(0, dev)
+    out = torch.empty((bench_mod.B_VISION, 512), device=dev, dtype=torch.float32)
+    ve.embed_pixels_device(px.data_ptr(), bench_mod.B_VISION, out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    torch.cuda.synchronize()
+    assert np.array_equal(got, out.cpu().numpy())
+    ve.close()
+
+
 @pytest.mark.parametrize("tower", ["vision", "text"])
 @pytest.mark.parametrize("which", ["default", "side", "null_array"])
 @pytest.mark.parametrize("entry", ["plain", "gather"])

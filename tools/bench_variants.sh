@@ -13,7 +13,7 @@ for i in $(seq 1 "$ROUNDS"); do
     if [[ "$extra" == *"|"* ]]; then vlib=${extra#*|}; extra=${extra%%|*}; fi
     if [ -n "$vlib" ]; then export CLIPGPU_LIB=$PWD/clip-embedder-rs_amd/lib/libclipgpu_$vlib.so; else unset CLIPGPU_LIB; fi
     log="gpurun_out/bv_${label}_$i.log"
-    timeout -k 10 300 python bench.py --steps 20 --warmup 5 ${BV_BASE:---no-cpu-baseline --no-fp8 --no-text --no-e2e --windows 3} \
+    timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full ${BV_BASE:---no-cpu-baseline --no-fp8 --no-text --no-e2e --windows 3} \
         $extra > "$log" 2>&1 || { echo "variant $label failed rc=$?"; tail -5 "$log"; exit 1; }
     python3 - "$label" "$i" "$log" >> "$OUT" <<'PY' || exit 1
 import json, sys

@@ -39,14 +39,14 @@ for s in $STEPS; do
       done
       cat gpurun_out/ab.log ;;
     bench_pin)  # the vision leg with PIN_TILES pinned (q,o,f,p), BENCH_PIN_ARGS extra bench args
-      run bench_pin_${PIN_TILES//,/_} 300 python bench.py --steps 20 --warmup 5 --tiles $PIN_TILES \
+      run bench_pin_${PIN_TILES//,/_} 300 python bench.py --steps 20 --warmup 5 --full --tiles $PIN_TILES \
           --no-cpu-baseline --no-fp8 --no-text --no-e2e ${BENCH_PIN_ARGS:-} || exit $? ;;
     ablate)  # marginal step time of each trunk op (tools/ablate.py; needs lib/libclipgpu_ablate.so:
              # make variant VNAME=ablate VDEFS=-DCLIPGPU_ABLATE)
       CLIPGPU_LIB=$PWD/clip-embedder-rs_amd/lib/libclipgpu_ablate.so run ablate 600 python tools/ablate.py || exit $?
       cp gpurun_out/ablate.log gpurun_out/ablate.jsonl ;;
     bench_quick)  # the bench without the CPU leg
-      run bench_quick 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline || exit $? ;;
+      run bench_quick 400 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline || exit $? ;;
     timeline)  # per-launch start / end of every trunk op with the lanes concurrent (tools/timeline.py)
       for spec in "vision 5 0" "vision 5 1" "text 3 0"; do
         run tl_$(echo $spec | tr ' ' _) 200 python tools/timeline.py $spec || exit $?
@@ -59,17 +59,17 @@ for s in $STEPS; do
     smoke)
       run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
     bench)
-      run bench 600 python bench.py --steps 20 --warmup 5 || exit $? ;;
+      run bench 600 python bench.py --steps 20 --warmup 5 --full || exit $? ;;
     breakdown)
-      run breakdown 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-fp8 --no-text --no-e2e --breakdown || exit $? ;;
+      run breakdown 300 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-fp8 --no-text --no-e2e --breakdown || exit $? ;;
     vtrace)  # kernel trace of the vision leg alone; per-kernel stats of the timed steps only (tools/trace_timed.py)
       run vtrace 300 rocprofv3 --kernel-trace --stats -d gpurun_out/vtrace -o run --output-format csv -- \
-          python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-fp8 --no-text --no-e2e --windows 0 || exit $?
+          python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-fp8 --no-text --no-e2e --windows 0 || exit $?
       VLANES=$(python3 -c "import json;print([json.loads(l) for l in open('gpurun_out/vtrace.log') if l.startswith('{')][-1]['lanes_env'])") || exit 1
       python3 tools/trace_timed.py gpurun_out/vtrace/run_kernel_trace.csv 10 gpurun_out/vtrace_timed_kernels.txt $VLANES || exit $? ;;
     prof)
       run rocprof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- \
-          python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline || exit $?
+          python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline || exit $?
       find gpurun_out/prof -name "*kernel_stats.csv" | head -3 ;;
     pmc)  # HBM bytes of the roofline kernel: FETCH_SIZE and WRITE_SIZE in separate passes,
           # GEMM tiles pinned to the ones the un-profiled bench autotuned (profiling skews tuning)
@@ -77,7 +77,7 @@ for s in $STEPS; do
       LANES=$(python3 -c "import json;print([json.loads(l) for l in open('gpurun_out/bench.log') if l.startswith('{')][-1]['lanes_env'])") || exit 1
       for C in FETCH_SIZE WRITE_SIZE; do
         run pmc_$C 600 rocprofv3 --pmc $C --output-format csv -d gpurun_out/pmc_bench/$C -o run -- \
-            python3 bench.py --steps 3 --warmup 1 --no-text --no-cpu-baseline --no-fp8 --no-e2e --windows 0 \
+            python3 bench.py --steps 3 --warmup 1 --full --no-text --no-cpu-baseline --no-fp8 --no-e2e --windows 0 \
             --tiles $TILES --lanes $LANES || exit $?
       done
       cp profiles/pmc_c_fc.json gpurun_out/pmc_c_fc.json  # merged into (copy back to profiles/ after the call)

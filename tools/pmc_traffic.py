@@ -7,7 +7,7 @@ SITE: c_fc (default), c_proj or out_proj.  TILES: the engine's gemm_tiles_env of
 ("q,o,f,p"); bench.py only takes a record whose tiles equal its own run's.
 
 FETCH_DIR / WRITE_DIR hold `rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE`
-counter_collection CSVs of the same `bench.py --no-text` command (separate passes: the
+counter_collection CSVs of the same `bench.py --full --no-text` command (separate passes: the
 two counters cannot share one on gfx950).  Per MI355X_MICROARCH.md §HBM: both counters
 are in KB; FETCH_SIZE reports half the bytes of wide coalesced streaming reads on gfx950,
 so it is doubled; WRITE_SIZE is exact for 16-byte-per-lane stores.

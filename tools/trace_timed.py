@@ -3,7 +3,7 @@
 
     python tools/trace_timed.py RUN_kernel_trace.csv STEPS [OUT.txt] [LANES]
 
-For a vision-only bench (`--no-text --no-fp8 --no-e2e --no-cpu-baseline`): after the engine's
+For a vision-only bench (`--full --no-text --no-fp8 --no-e2e --no-cpu-baseline`): after the engine's
 creation-time tuning, the trace ends with W warmup steps, the STEPS timed steps, then the c_fc
 profiling pass (1 warmup + P = max(3, STEPS // 2) steps, lanes serialized), then the same P + 1
 steps with the lanes concurrent (the concurrent site profile; skipped when finding the period).  Every step issues the
