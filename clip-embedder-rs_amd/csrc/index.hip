@@ -1,0 +1,207 @@
+// The embedding index of include/clipgpu.h: a gallery of embeddings that stays on one GPU between
+// calls, searched by the fused top-k kernels (kernels/topk.hip) -- what the reference's users do
+// with the embeddings (README.md:76-82, examples/search.rs, Clip::rank_images src/clip.rs:134-170)
+// without the [queries][gallery] score matrix or a host sort.
+//
+// Everything is allocated at creation: the gallery at its fixed capacity and one work area (the
+// search workspace + staging for the host-buffer search's query chunk and results).  A mutex
+// serialises the callers of a handle; on the device, each operation waits for the event recorded
+// after the previous one, so an add on one stream followed by a search on another is ordered and
+// two searches never share the workspace at once.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <mutex>
+#include <string>
+
+#include "../../include/clipgpu.h"
+#include "bounce.hpp"
+#include "host/api_util.hpp"
+#include "kernels/kernels.hpp"
+
+using namespace clipgpu;
+
+namespace {
+
+#define IX_CHECK(expr)                                                                                    \
+  do {                                                                                                    \
+    hipError_t _e = (expr);                                                                               \
+    if (_e != hipSuccess) {                                                                               \
+      (void)hipGetLastError();                                                                            \
+      throw ClipErr(CLIPGPU_ERR_DEVICE, std::string("HIP error: ") + hipGetErrorString(_e) + " (" #expr ")"); \
+    }                                                                                                     \
+  } while (0)
+
+constexpr int64_t kQueryChunk = 256;  // queries per launch: 4 query tiles
+constexpr int kMaxBlocks = 1024;      // phase-1 blocks per launch the workspace is sized for (4 per CU)
+inline size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
+
+}  // namespace
+
+struct clipgpu_index {
+  std::mutex mu;
+  int device = 0;
+  int64_t E = 0, capacity = 0, size = 0;
+  float* gallery = nullptr;  // [capacity][E]
+  char* work = nullptr;      // ws | staged queries | staged indices | staged scores
+  int ws_blocks = 0;         // phase-1 blocks the workspace holds: min(kMaxBlocks, 4 * 64-row tiles of capacity)
+  float* st_q = nullptr;
+  int64_t* st_idx = nullptr;
+  float* st_score = nullptr;
+  hipStream_t stream = nullptr;  // the host-buffer forms' stream
+  hipEvent_t done = nullptr;     // recorded after every device-side operation
+};
+
+namespace {
+
+void order_after_last(clipgpu_index* ix, hipStream_t s) { IX_CHECK(hipStreamWaitEvent(s, ix->done, 0)); }
+void mark_last(clipgpu_index* ix, hipStream_t s) { IX_CHECK(hipEventRecord(ix->done, s)); }
+
+void check_add(const clipgpu_index* ix, const float* rows, int64_t n) {
+  if (!ix || !rows) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+  if (n <= 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
+}
+
+void check_search(const clipgpu_index* ix, const float* q, int64_t nq, int64_t k, const int64_t* idx,
+                  const float* score) {
+  if (!ix || !q || !idx || !score) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+  if (nq <= 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
+  if (k < 1 || k > CLIPGPU_TOPK_MAX)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "k must be in 1.." + std::to_string(CLIPGPU_TOPK_MAX) +
+                                           " (clipgpu_similarity gives the whole matrix)");
+}
+
+// Searches d_q [nq][E] in chunks of kQueryChunk rows on `s` (ordered after the handle's last operation).
+void search_on(clipgpu_index* ix, const float* d_q, int64_t nq, int64_t k, float scale, float bias, int64_t* d_idx,
+               float* d_score, hipStream_t s) {
+  order_after_last(ix, s);
+  for (int64_t q0 = 0; q0 < nq; q0 += kQueryChunk) {
+    const int rows = (int)std::min(kQueryChunk, nq - q0);
+    const TopkPlan p = topk_plan(ix->size, (rows + 63) / 64, ix->ws_blocks);
+    IX_CHECK(launch_topk(d_q + q0 * ix->E, rows, ix->gallery, (int)ix->size, (int)ix->E, scale, bias, (int)k, p,
+                         ix->work, d_idx + q0 * k, d_score + q0 * k, s));
+  }
+  mark_last(ix, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int clipgpu_index_create(int device, int64_t E, int64_t capacity, clipgpu_index** out) {
+  return guarded([&]() {
+    if (!out) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL out");
+    *out = nullptr;
+    if (E <= 0 || E % 16) throw ClipErr(CLIPGPU_ERR_INVALID, "Shape error: embedding dim must be a multiple of 16");
+    if (capacity <= 0) throw ClipErr(CLIPGPU_ERR_INVALID, "capacity must be positive");
+    if (capacity >= (1LL << 31) || E > (1 << 20) || capacity > (1LL << 46) / (E * 4))
+      throw ClipErr(CLIPGPU_ERR_INVALID, "Shape error: index too large (capacity < 2^31 rows)");
+    if (device < 0) throw ClipErr(CLIPGPU_ERR_INVALID, "bad device");
+    IX_CHECK(hipSetDevice(device));
+    clipgpu_index* ix = new clipgpu_index;
+    ix->device = device;
+    ix->E = E;
+    ix->capacity = capacity;
+    ix->ws_blocks = (int)std::min<int64_t>(kMaxBlocks, 4 * ((capacity + 63) / 64));
+    const size_t ws = align256((size_t)ix->ws_blocks * 64 * kTopkMax * 8);
+    const size_t sq = align256((size_t)kQueryChunk * E * 4), si = align256((size_t)kQueryChunk * kTopkMax * 8);
+    const size_t ss = align256((size_t)kQueryChunk * kTopkMax * 4);
+    hipError_t err = hipMalloc((void**)&ix->gallery, (size_t)capacity * E * 4);
+    if (err == hipSuccess) err = hipMalloc((void**)&ix->work, ws + sq + si + ss);
+    if (err == hipSuccess) err = hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking);
+    if (err == hipSuccess) err = hipEventCreateWithFlags(&ix->done, hipEventDisableTiming);
+    if (err != hipSuccess) {
+      clipgpu_index_destroy(ix);
+      IX_CHECK(err);
+    }
+    ix->st_q = (float*)(ix->work + ws);
+    ix->st_idx = (int64_t*)(ix->work + ws + sq);
+    ix->st_score = (float*)(ix->work + ws + sq + si);
+    *out = ix;
+  });
+}
+
+void clipgpu_index_destroy(clipgpu_index* ix) {
+  if (!ix) return;
+  (void)hipSetDevice(ix->device);
+  if (ix->done) {
+    (void)hipEventSynchronize(ix->done);  // the last operation has left the buffers
+    (void)hipEventDestroy(ix->done);
+  }
+  if (ix->stream) (void)hipStreamDestroy(ix->stream);
+  if (ix->work) (void)hipFree(ix->work);
+  if (ix->gallery) (void)hipFree(ix->gallery);
+  delete ix;
+}
+
+int64_t clipgpu_index_size(const clipgpu_index* ix) {
+  if (!ix) return 0;
+  std::lock_guard<std::mutex> lk(const_cast<clipgpu_index*>(ix)->mu);
+  return ix->size;
+}
+
+int clipgpu_index_clear(clipgpu_index* ix) {
+  return guarded([&]() {
+    if (!ix) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    ix->size = 0;  // a later add overwrites the rows only after the last search (the `done` event)
+  });
+}
+
+int clipgpu_index_add_device(clipgpu_index* ix, const float* d_rows, int64_t n, void* stream) {
+  return guarded([&]() {
+    check_add(ix, d_rows, n);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (n > ix->capacity - ix->size) throw ClipErr(CLIPGPU_ERR_INVALID, "index full");
+    IX_CHECK(hipSetDevice(ix->device));
+    hipStream_t s = (hipStream_t)stream;
+    order_after_last(ix, s);
+    IX_CHECK(hipMemcpyAsync(ix->gallery + ix->size * ix->E, d_rows, (size_t)n * ix->E * 4, hipMemcpyDeviceToDevice, s));
+    mark_last(ix, s);
+    ix->size += n;
+  });
+}
+
+int clipgpu_index_add(clipgpu_index* ix, const float* rows, int64_t n) {
+  return guarded([&]() {
+    check_add(ix, rows, n);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (n > ix->capacity - ix->size) throw ClipErr(CLIPGPU_ERR_INVALID, "index full");
+    IX_CHECK(hipSetDevice(ix->device));
+    IX_CHECK(hipEventSynchronize(ix->done));
+    IX_CHECK(copy_h2d(ix->gallery + ix->size * ix->E, rows, (size_t)n * ix->E * 4));
+    ix->size += n;
+  });
+}
+
+int clipgpu_index_search_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k, float logit_scale,
+                                float logit_bias, int64_t* d_idx, float* d_score, void* stream) {
+  return guarded([&]() {
+    check_search(ix, d_queries, nq, k, d_idx, d_score);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (ix->size == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");  // an empty gallery
+    IX_CHECK(hipSetDevice(ix->device));
+    search_on(ix, d_queries, nq, k, logit_scale, logit_bias, d_idx, d_score, (hipStream_t)stream);
+  });
+}
+
+int clipgpu_index_search(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, float logit_scale,
+                         float logit_bias, int64_t* out_idx, float* out_score) {
+  return guarded([&]() {
+    check_search(ix, queries, nq, k, out_idx, out_score);
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (ix->size == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
+    IX_CHECK(hipSetDevice(ix->device));
+    IX_CHECK(hipEventSynchronize(ix->done));  // the staging buffers are free
+    for (int64_t q0 = 0; q0 < nq; q0 += kQueryChunk) {
+      const int64_t rows = std::min(kQueryChunk, nq - q0);
+      IX_CHECK(copy_h2d(ix->st_q, queries + q0 * ix->E, (size_t)rows * ix->E * 4));
+      search_on(ix, ix->st_q, rows, k, logit_scale, logit_bias, ix->st_idx, ix->st_score, ix->stream);
+      IX_CHECK(hipStreamSynchronize(ix->stream));
+      IX_CHECK(copy_d2h(out_idx + q0 * k, ix->st_idx, (size_t)rows * k * 8));
+      IX_CHECK(copy_d2h(out_score + q0 * k, ix->st_score, (size_t)rows * k * 4));
+    }
+  });
+}
+
+}  // extern "C"

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 namespace clipgpu {
 
 enum DType { DT_BF16 = 0, DT_F16 = 1 };
@@ -175,6 +177,21 @@ hipError_t launch_resize(const uint8_t* raw, uint8_t* tmp, const int* ints, cons
 enum SimAct { SIM_SOFTMAX = 0, SIM_SIGMOID = 1, SIM_LOGITS = 2 };
 hipError_t launch_similarity(const float* img, int ni, const float* txt, int nt, int E, float scale, float bias,
                              int activation, int axis, float* out, hipStream_t s);
+
+// Fused top-k search (kernels/topk.hip): per query row the k best gallery rows by
+// fmaf(q[i] . g[j], scale, bias) -- bit-identical to launch_similarity's logits -- in the order of
+// topk_key.hpp, best first: out_idx [nq][k] (int64, -1 beyond min(k, N)), out_score [nq][k] (f32,
+// -inf there).  The gallery is cut into n_spans spans of span_cols columns (a multiple of 64); ws
+// holds ceil(nq / 64) * 64 * n_spans * k entries of 8 bytes.  1 <= k <= kTopkMax, E % 16 == 0.
+constexpr int kTopkMax = 128;
+struct TopkPlan { int span_cols, n_spans; };
+// The span cut for N gallery rows and q_tiles 64-query tiles with at most max_blocks phase-1 blocks
+// (the workspace bound): as many spans as tiles and max_blocks allow, or g_topk_span_cols columns per
+// span when that test hook is set (clipgpu_test_topk_span_cols; 0 = off).
+extern std::atomic<long> g_topk_span_cols;
+TopkPlan topk_plan(long N, int q_tiles, int max_blocks);
+hipError_t launch_topk(const float* q, int nq, const float* g, int N, int E, float scale, float bias, int k,
+                       const TopkPlan& p, void* ws, int64_t* out_idx, float* out_score, hipStream_t s);
 
 // out[r] = in[r] / max(||in[r]||_2, 1e-12)
 hipError_t launch_l2norm(const float* in, float* out, int B, int E, hipStream_t s);

@@ -20,6 +20,7 @@
 #include "host/api_util.hpp"
 #include "kernels/common.hpp"
 #include "kernels/kernels.hpp"
+#include "kernels/topk_key.hpp"
 
 using namespace clipgpu;
 
@@ -140,6 +141,22 @@ int clipgpu_test_gemm_chunk_rows(int64_t rows) {
   return guarded([&]() {
     if (rows < 0) throw ClipErr(CLIPGPU_ERR_INVALID, "rows < 0");
     g_gemm_chunk_cap = (long)rows;
+  });
+}
+
+int clipgpu_test_topk_span_cols(int64_t cols) {
+  return guarded([&]() {
+    if (cols < 0 || cols % 64) throw ClipErr(CLIPGPU_ERR_INVALID, "cols must be a multiple of 64 (0 = default)");
+    g_topk_span_cols.store((long)cols);
+  });
+}
+
+int clipgpu_test_topk_key(float score, uint32_t index, uint64_t* key) {
+  return guarded([&]() {
+    if (!key) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL key");
+    uint32_t bits;
+    std::memcpy(&bits, &score, 4);
+    *key = topk_key(bits, index);
   });
 }
 

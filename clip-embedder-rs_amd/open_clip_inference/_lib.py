@@ -55,6 +55,15 @@ _PROTOS = [
     ("clipgpu_tokenizer_vocab_size", c_int64, [c_void_p]),
     ("clipgpu_similarity", c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_float, c_float, c_int, c_int, c_void_p]),
     ("clipgpu_similarity_device", c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_float, c_float, c_int, c_int, c_void_p, c_void_p]),
+    ("clipgpu_index_create", c_int, [c_int, c_int64, c_int64, POINTER(c_void_p)]),
+    ("clipgpu_index_destroy", None, [c_void_p]),
+    ("clipgpu_index_size", c_int64, [c_void_p]),
+    ("clipgpu_index_clear", c_int, [c_void_p]),
+    ("clipgpu_index_add", c_int, [c_void_p, c_void_p, c_int64]),
+    ("clipgpu_index_add_device", c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    ("clipgpu_index_search", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_void_p, c_void_p]),
+    ("clipgpu_index_search_device", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_void_p, c_void_p,
+                                            c_void_p]),
     ("clipgpu_comm_unique_id", c_int, [c_void_p]),
     ("clipgpu_comm_init_rank", c_int, [c_void_p, c_void_p, c_int, c_int]),
     ("clipgpu_comm_info", c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
@@ -68,6 +77,8 @@ _PROTOS = [
     # include/clipgpu_testing.h
     ("clipgpu_test_gemm", c_int, [c_int, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("clipgpu_test_gemm_chunk_rows", c_int, [c_int64]),
+    ("clipgpu_test_topk_span_cols", c_int, [c_int64]),
+    ("clipgpu_test_topk_key", c_int, [c_float, ctypes.c_uint32, POINTER(c_uint64)]),
     ("clipgpu_test_gemm_lnf", c_int, [c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_float, c_int, c_void_p]),
     ("clipgpu_test_attention", c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p]),

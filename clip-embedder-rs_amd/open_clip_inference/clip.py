@@ -121,6 +121,27 @@ class Clip:
             out.append(res)
         return out
 
+    # -- a gallery resident on the GPU, searched top-k (README.md:76-82, examples/search.rs) ----
+    def build_index(self, images, capacity=None):
+        """Embeds ``images`` and stores them in an ``EmbeddingIndex`` on the vision engine's first
+        device (``capacity`` rows, default: as many as there are images); image i is index i."""
+        from .index import EmbeddingIndex
+        embs = self.vision.embed_images(images)
+        index = EmbeddingIndex(embs.shape[1], len(embs) if capacity is None else int(capacity),
+                               self.vision.session.devices[0])
+        index.add(embs)
+        return index
+
+    def search(self, index, texts: Sequence[str], k: int) -> List[List[Tuple[int, float]]]:
+        """Semantic search (examples/search.rs; rank_images, src/clip.rs:134-170, cut to its k best):
+        per text the k best rows of ``index`` as (gallery index, logit), best first, equal logits by
+        ascending index.  The logits use the model's logit_scale / logit_bias (defaults 1.0 / 0.0).
+        Logits, not probabilities: a softmax over the gallery needs every score of the row and
+        stays with ``rank_images_many``."""
+        scale, bias = self._scale_bias()
+        idx, score = index.search(self.text.embed_texts(texts), k, float(scale), float(bias))
+        return [[(int(i), float(s)) for i, s in zip(ri, rs) if i >= 0] for ri, rs in zip(idx, score)]
+
     @staticmethod
     def softmax(logits) -> np.ndarray:  # src/clip.rs:172-179 (f32, sequential sum; facade.cpp)
         # host-only library (no HIP / RCCL): usable on a host without ROCm

@@ -28,6 +28,8 @@
 extern "C" {
 #endif
 
+/* Stays 4 with the embedding index section: that change only adds symbols; every existing entry
+ * point keeps its signature, its behaviour and its bits. */
 #define CLIPGPU_ABI_VERSION 4
 
 enum clipgpu_status {
@@ -254,6 +256,42 @@ int clipgpu_similarity(int device, const float* img, int64_t n_img, const float*
 int clipgpu_similarity_device(const float* d_img, int64_t n_img, const float* d_txt, int64_t n_txt, int64_t E,
                               float logit_scale, float logit_bias, int activation, int axis, float* d_out,
                               void* stream);
+
+/* ---- embedding index: a device-resident gallery with fused top-k search ----------------------
+ * What the reference's users do with the embeddings: store the image embeddings and "search with the
+ * text embedding through images using cosine similarity" (README.md:76-82; examples/search.rs),
+ * best first as Clip::rank_images returns them (src/clip.rs:134-170).  The gallery stays on GPU
+ * `device` between calls (the *_device embed entry points can feed it without a host round trip);
+ * a search returns only the k best rows per query, the [n_q][N] score matrix never exists.
+ *   score(i, j) = dot(queries[i], gallery[j]).mul_add(logit_scale, logit_bias) -- bit-identical to
+ *     clipgpu_similarity(..., CLIPGPU_SIM_LOGITS) on the same inputs (logits, not probabilities: a
+ *     softmax over the gallery needs the whole row and stays with clipgpu_similarity);
+ *   order: descending score, equal scores by ascending gallery index (the reference's stable
+ *     sort_by(partial_cmp), src/clip.rs:160-166); +0.0 == -0.0; a NaN score ranks below -inf
+ *     (L2-normalised embeddings never produce one).
+ * Rows are appended in call order and an index is a row's position in that order.  E % 16 == 0,
+ * capacity < 2^31 rows, fixed at creation: the gallery, one search workspace (at most 64 MiB) and
+ * the host forms' staging are allocated there and never reallocated; an add beyond the capacity is
+ * CLIPGPU_ERR_INVALID "index full" and leaves the index unchanged.  1 <= k <= CLIPGPU_TOPK_MAX
+ * (larger k: the whole matrix via clipgpu_similarity).  out_idx [nq][k] int64, out_score [nq][k] f32
+ * (the logits' own bits); slots beyond min(k, size) hold index -1 and score -inf.  Any nq: queries
+ * run in chunks sized to the workspace.  nq <= 0 or an empty index: "Empty batch".
+ * A handle serialises its callers (mutex).  The _device forms take device pointers on `device`, are
+ * ordered on `stream` (NULL = the legacy default stream) and return without synchronising; the
+ * handle also orders each operation after its previous one by an event, so an add on one stream
+ * followed by a search on another sees the added rows.  The host forms synchronise. */
+typedef struct clipgpu_index clipgpu_index;
+#define CLIPGPU_TOPK_MAX 128
+int clipgpu_index_create(int device, int64_t E, int64_t capacity, clipgpu_index** out);
+void clipgpu_index_destroy(clipgpu_index* ix);
+int64_t clipgpu_index_size(const clipgpu_index* ix); /* rows added so far */
+int clipgpu_index_clear(clipgpu_index* ix);          /* size 0; the capacity stays */
+int clipgpu_index_add(clipgpu_index* ix, const float* rows, int64_t n); /* host rows [n][E] */
+int clipgpu_index_add_device(clipgpu_index* ix, const float* d_rows, int64_t n, void* stream);
+int clipgpu_index_search(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, float logit_scale,
+                         float logit_bias, int64_t* out_idx, float* out_score);
+int clipgpu_index_search_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k, float logit_scale,
+                                float logit_bias, int64_t* d_idx, float* d_score, void* stream);
 
 /* ---- data-parallel sharding + the RCCL all-gather (north_star: "batches shard
  * data-parallel across the 8 GPUs of one node with an RCCL all-gather over xGMI only for the final

@@ -165,6 +165,14 @@ int clipgpu_test_profile_timeline(struct clipgpu_engine* e, int64_t n_max, doubl
  * gathered entry points: a negative count, or zero rows in all ("Empty batch"). */
 int clipgpu_test_gather_plan(int nranks, const int64_t* rows, int64_t* off, int* equal);
 
+/* Columns per gallery span of clipgpu_index_search (a multiple of 64; 0 = the default cut, which
+ * fills the GPU), process-wide and atomic, for every search started afterwards: small galleries then
+ * run many spans and the merge.  The result never depends on it. */
+int clipgpu_test_topk_span_cols(int64_t cols);
+/* Host only: the search's order key (csrc/kernels/topk_key.hpp) of (score, gallery index): a larger
+ * key ranks first. */
+int clipgpu_test_topk_key(float score, uint32_t index, uint64_t* key);
+
 #ifdef __cplusplus
 }
 #endif

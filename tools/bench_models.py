@@ -163,6 +163,68 @@ def similarity_leg(ni=65536, nt=1000, E=512, steps=5, warmup=2):
                       "max_abs_err_vs_torch": err}), flush=True)
 
 
+def topk_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2):
+    """Semantic search over a device-resident gallery of N embeddings, Q = 256 and Q = 1 queries:
+    the fused top-k search (clipgpu_index_search_device) against the same result by the full-matrix
+    path (clipgpu_similarity_device logits into a [Q][N] tensor, then torch.topk on the device).  The
+    two alternate in one process; per path the median and the spread of `runs` device-event timings
+    after `warmup` rounds.  Both do 2 Q N E f32-MFMA FLOP; the fused path's floor is the larger of
+    that over the f32 MFMA peak (157.3 TF) and one read of the gallery over the HBM peak (8 TB/s)."""
+    import ctypes
+    from open_clip_inference import EmbeddingIndex
+    torch.manual_seed(0)
+    L = _lib.lib()
+    s = torch.cuda.current_stream().cuda_stream
+    g = torch.nn.functional.normalize(torch.randn(N, E, device="cuda"), dim=1)
+    ix = EmbeddingIndex(E, N)
+    ix.add_device(g.data_ptr(), N, s)
+    for Q in (256, 1):
+        q = torch.nn.functional.normalize(torch.randn(Q, E, device="cuda"), dim=1)
+        mat = torch.empty(Q, N, device="cuda")
+        f_idx = torch.empty((Q, k), dtype=torch.int64, device="cuda")
+        f_score = torch.empty((Q, k), device="cuda")
+        base = {}
+
+        def fused():
+            ix.search_device(q.data_ptr(), Q, k, f_idx.data_ptr(), f_score.data_ptr(), 100.0, 0.0, s)
+
+        def baseline():
+            _lib.check(L.clipgpu_similarity_device(ctypes.c_void_p(q.data_ptr()), Q, ctypes.c_void_p(g.data_ptr()), N,
+                                                   E, 100.0, 0.0, 2, 1, ctypes.c_void_p(mat.data_ptr()),
+                                                   ctypes.c_void_p(s)))
+            base["score"], base["idx"] = torch.topk(mat, k, dim=1)
+
+        ms = {"fused": [], "baseline": []}
+        for rnd in range(warmup + runs):
+            for name, fn in (("fused", fused), ("baseline", baseline)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                if rnd >= warmup:
+                    ms[name].append(e0.elapsed_time(e1))
+        # the same result: scores bit for bit; indices once the baseline's ties are put in index order
+        b_idx, b_score = base["idx"].cpu().numpy(), base["score"].cpu().numpy()
+        order = np.lexsort((b_idx, -b_score.astype(np.float64)), axis=1)
+        b_idx, b_score = np.take_along_axis(b_idx, order, 1), np.take_along_axis(b_score, order, 1)
+        assert np.array_equal(f_score.cpu().numpy().view(np.uint32), b_score.view(np.uint32)), "scores differ"
+        assert np.array_equal(f_idx.cpu().numpy(), b_idx), "indices differ"
+        flop = 2.0 * Q * N * E
+        t_mfma, t_hbm = flop / 157.3e12, N * E * 4 / 8.0e12
+        out = {"measure": "topk_search", "Q": Q, "N": N, "E": E, "k": k, "runs": runs, "same_indices": True,
+               "fused_floor": "MFMA-bound" if t_mfma >= t_hbm else "HBM-bound",
+               "fused_floor_ms": round(max(t_mfma, t_hbm) * 1e3, 3)}
+        for name, v in ms.items():
+            med = float(np.median(v))
+            out[name + "_ms_median"] = round(med, 3)
+            out[name + "_ms_min_max"] = [round(min(v), 3), round(max(v), 3)]
+            out[name + "_tflops_f32"] = round(flop / (med * 1e-3) / 1e12, 2)
+        out["fused_speedup"] = round(out["baseline_ms_median"] / out["fused_ms_median"], 2)
+        print(json.dumps(out), flush=True)
+    ix.close()
+
+
 def latency_leg(steps=50, warmup=10):
     """Single-item latency (the reference's embed_image / embed_text calls, B = 1) through the
     host entry points: pinned staging + H2D + forward + D2H + synchronise, ViT-B/32."""
@@ -206,6 +268,8 @@ if __name__ == "__main__":
         similarity_leg()
     if "latency" in which:
         latency_leg()
+    if "topk" in which:  # the embedding index's fused search vs similarity + torch.topk
+        topk_leg()
     if "so400m" in which:
         device_leg("so400m_vision", SO400M_16_SIGLIP2_384_CFG, 0, 128)
     if "h14" in which:
