@@ -1,4 +1,4 @@
-// Persistent host copy workers for the host entry points' pinned staging (engine.hip run_host_shard and
+// Persistent host copy workers for the host entry points' pinned staging (engine/host_path.hip run_host_shard and
 // the decoded-image path): one pool per process, its workers parked on a condition variable between jobs,
 // so a call pays no thread creation (round 5 spawned up to 8 std::threads per chunk).  One host thread moves
 // ~10 GB/s; the staging copies of a 256-image u8 batch (38.5 MB) or of 640x480 RGB8 images (236 MB) need

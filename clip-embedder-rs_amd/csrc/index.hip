@@ -16,21 +16,13 @@
 
 #include "../../include/clipgpu.h"
 #include "bounce.hpp"
+#include "hip_check.hpp"
 #include "host/api_util.hpp"
 #include "kernels/kernels.hpp"
 
 using namespace clipgpu;
 
 namespace {
-
-#define IX_CHECK(expr)                                                                                    \
-  do {                                                                                                    \
-    hipError_t _e = (expr);                                                                               \
-    if (_e != hipSuccess) {                                                                               \
-      (void)hipGetLastError();                                                                            \
-      throw ClipErr(CLIPGPU_ERR_DEVICE, std::string("HIP error: ") + hipGetErrorString(_e) + " (" #expr ")"); \
-    }                                                                                                     \
-  } while (0)
 
 constexpr int64_t kQueryChunk = 256;  // queries per launch: 4 query tiles
 constexpr int kMaxBlocks = 1024;      // phase-1 blocks per launch the workspace is sized for (4 per CU)
@@ -54,8 +46,8 @@ struct clipgpu_index {
 
 namespace {
 
-void order_after_last(clipgpu_index* ix, hipStream_t s) { IX_CHECK(hipStreamWaitEvent(s, ix->done, 0)); }
-void mark_last(clipgpu_index* ix, hipStream_t s) { IX_CHECK(hipEventRecord(ix->done, s)); }
+void order_after_last(clipgpu_index* ix, hipStream_t s) { HIP_CHECK(hipStreamWaitEvent(s, ix->done, 0)); }
+void mark_last(clipgpu_index* ix, hipStream_t s) { HIP_CHECK(hipEventRecord(ix->done, s)); }
 
 void check_add(const clipgpu_index* ix, const float* rows, int64_t n) {
   if (!ix || !rows) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
@@ -78,7 +70,7 @@ void search_on(clipgpu_index* ix, const float* d_q, int64_t nq, int64_t k, float
   for (int64_t q0 = 0; q0 < nq; q0 += kQueryChunk) {
     const int rows = (int)std::min(kQueryChunk, nq - q0);
     const TopkPlan p = topk_plan(ix->size, (rows + 63) / 64, ix->ws_blocks);
-    IX_CHECK(launch_topk(d_q + q0 * ix->E, rows, ix->gallery, (int)ix->size, (int)ix->E, scale, bias, (int)k, p,
+    HIP_CHECK(launch_topk(d_q + q0 * ix->E, rows, ix->gallery, (int)ix->size, (int)ix->E, scale, bias, (int)k, p,
                          ix->work, d_idx + q0 * k, d_score + q0 * k, s));
   }
   mark_last(ix, s);
@@ -97,7 +89,7 @@ int clipgpu_index_create(int device, int64_t E, int64_t capacity, clipgpu_index*
     if (capacity >= (1LL << 31) || E > (1 << 20) || capacity > (1LL << 46) / (E * 4))
       throw ClipErr(CLIPGPU_ERR_INVALID, "Shape error: index too large (capacity < 2^31 rows)");
     if (device < 0) throw ClipErr(CLIPGPU_ERR_INVALID, "bad device");
-    IX_CHECK(hipSetDevice(device));
+    HIP_CHECK(hipSetDevice(device));
     clipgpu_index* ix = new clipgpu_index;
     ix->device = device;
     ix->E = E;
@@ -112,7 +104,7 @@ int clipgpu_index_create(int device, int64_t E, int64_t capacity, clipgpu_index*
     if (err == hipSuccess) err = hipEventCreateWithFlags(&ix->done, hipEventDisableTiming);
     if (err != hipSuccess) {
       clipgpu_index_destroy(ix);
-      IX_CHECK(err);
+      HIP_CHECK(err);
     }
     ix->st_q = (float*)(ix->work + ws);
     ix->st_idx = (int64_t*)(ix->work + ws + sq);
@@ -153,10 +145,10 @@ int clipgpu_index_add_device(clipgpu_index* ix, const float* d_rows, int64_t n, 
     check_add(ix, d_rows, n);
     std::lock_guard<std::mutex> lk(ix->mu);
     if (n > ix->capacity - ix->size) throw ClipErr(CLIPGPU_ERR_INVALID, "index full");
-    IX_CHECK(hipSetDevice(ix->device));
+    HIP_CHECK(hipSetDevice(ix->device));
     hipStream_t s = (hipStream_t)stream;
     order_after_last(ix, s);
-    IX_CHECK(hipMemcpyAsync(ix->gallery + ix->size * ix->E, d_rows, (size_t)n * ix->E * 4, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(ix->gallery + ix->size * ix->E, d_rows, (size_t)n * ix->E * 4, hipMemcpyDeviceToDevice, s));
     mark_last(ix, s);
     ix->size += n;
   });
@@ -167,9 +159,9 @@ int clipgpu_index_add(clipgpu_index* ix, const float* rows, int64_t n) {
     check_add(ix, rows, n);
     std::lock_guard<std::mutex> lk(ix->mu);
     if (n > ix->capacity - ix->size) throw ClipErr(CLIPGPU_ERR_INVALID, "index full");
-    IX_CHECK(hipSetDevice(ix->device));
-    IX_CHECK(hipEventSynchronize(ix->done));
-    IX_CHECK(copy_h2d(ix->gallery + ix->size * ix->E, rows, (size_t)n * ix->E * 4));
+    HIP_CHECK(hipSetDevice(ix->device));
+    HIP_CHECK(hipEventSynchronize(ix->done));
+    HIP_CHECK(copy_h2d(ix->gallery + ix->size * ix->E, rows, (size_t)n * ix->E * 4));
     ix->size += n;
   });
 }
@@ -180,7 +172,7 @@ int clipgpu_index_search_device(clipgpu_index* ix, const float* d_queries, int64
     check_search(ix, d_queries, nq, k, d_idx, d_score);
     std::lock_guard<std::mutex> lk(ix->mu);
     if (ix->size == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");  // an empty gallery
-    IX_CHECK(hipSetDevice(ix->device));
+    HIP_CHECK(hipSetDevice(ix->device));
     search_on(ix, d_queries, nq, k, logit_scale, logit_bias, d_idx, d_score, (hipStream_t)stream);
   });
 }
@@ -191,15 +183,15 @@ int clipgpu_index_search(clipgpu_index* ix, const float* queries, int64_t nq, in
     check_search(ix, queries, nq, k, out_idx, out_score);
     std::lock_guard<std::mutex> lk(ix->mu);
     if (ix->size == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
-    IX_CHECK(hipSetDevice(ix->device));
-    IX_CHECK(hipEventSynchronize(ix->done));  // the staging buffers are free
+    HIP_CHECK(hipSetDevice(ix->device));
+    HIP_CHECK(hipEventSynchronize(ix->done));  // the staging buffers are free
     for (int64_t q0 = 0; q0 < nq; q0 += kQueryChunk) {
       const int64_t rows = std::min(kQueryChunk, nq - q0);
-      IX_CHECK(copy_h2d(ix->st_q, queries + q0 * ix->E, (size_t)rows * ix->E * 4));
+      HIP_CHECK(copy_h2d(ix->st_q, queries + q0 * ix->E, (size_t)rows * ix->E * 4));
       search_on(ix, ix->st_q, rows, k, logit_scale, logit_bias, ix->st_idx, ix->st_score, ix->stream);
-      IX_CHECK(hipStreamSynchronize(ix->stream));
-      IX_CHECK(copy_d2h(out_idx + q0 * k, ix->st_idx, (size_t)rows * k * 8));
-      IX_CHECK(copy_d2h(out_score + q0 * k, ix->st_score, (size_t)rows * k * 4));
+      HIP_CHECK(hipStreamSynchronize(ix->stream));
+      HIP_CHECK(copy_d2h(out_idx + q0 * k, ix->st_idx, (size_t)rows * k * 8));
+      HIP_CHECK(copy_d2h(out_score + q0 * k, ix->st_score, (size_t)rows * k * 4));
     }
   });
 }

@@ -16,6 +16,7 @@
 #include "../../include/clipgpu.h"
 #include "../../include/clipgpu_testing.h"
 #include "bounce.hpp"
+#include "hip_check.hpp"
 #include "host/copy_pool.hpp"
 #include "host/api_util.hpp"
 #include "kernels/common.hpp"
@@ -26,17 +27,11 @@ using namespace clipgpu;
 
 namespace {
 
-#define TCHECK(expr)                                                                                  \
-  do {                                                                                                \
-    hipError_t _e = (expr);                                                                           \
-    if (_e != hipSuccess) throw ClipErr(CLIPGPU_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
 struct DevBuf {
   void* p = nullptr;
   explicit DevBuf(size_t n) {
-    TCHECK(hipMalloc(&p, n ? n : 16));
-    TCHECK(hipMemset(p, 0, n ? n : 16));
+    HIP_CHECK(hipMalloc(&p, n ? n : 16));
+    HIP_CHECK(hipMemset(p, 0, n ? n : 16));
   }
   ~DevBuf() { (void)hipFree(p); }
   template <typename T> T* as() const { return (T*)p; }
@@ -73,15 +68,15 @@ __global__ void clock_probe_kernel(unsigned long long* out, unsigned long long t
   if (lane < 2) out[lane] = lane == 0 ? t1 - t0 : r - r0;
 }
 
-void up(void* d, const void* h, size_t n) { TCHECK(copy_h2d(d, h, n)); }
-void down(void* h, const void* d, size_t n) { TCHECK(copy_d2h(h, d, n)); }
+void up(void* d, const void* h, size_t n) { HIP_CHECK(copy_h2d(d, h, n)); }
+void down(void* h, const void* d, size_t n) { HIP_CHECK(copy_d2h(h, d, n)); }
 
 // f32 host -> 16-bit device
 void up16(DType dt, void* d16, const float* h, size_t n) {
   DevBuf tmp(n * 4);
   up(tmp.p, h, n * 4);
-  TCHECK(launch_cast_f32(dt, tmp.as<float>(), d16, (long)n, nullptr));
-  TCHECK(hipDeviceSynchronize());
+  HIP_CHECK(launch_cast_f32(dt, tmp.as<float>(), d16, (long)n, nullptr));
+  HIP_CHECK(hipDeviceSynchronize());
 }
 
 template <typename T>
@@ -94,8 +89,8 @@ void down16(DType dt, float* h, const void* d16, size_t n) {
   DevBuf tmp(n * 4);
   if (dt == DT_BF16) hipLaunchKernelGGL(widen<__bf16>, dim3(1024), dim3(256), 0, nullptr, (const __bf16*)d16, tmp.as<float>(), (long)n);
   else hipLaunchKernelGGL(widen<_Float16>, dim3(1024), dim3(256), 0, nullptr, (const _Float16*)d16, tmp.as<float>(), (long)n);
-  TCHECK(hipGetLastError());
-  TCHECK(hipDeviceSynchronize());
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipDeviceSynchronize());
   down(h, tmp.p, n * 4);
 }
 
@@ -129,8 +124,8 @@ int clipgpu_test_gemm(int dtype, int mode, int act, int64_t M, int64_t N, int64_
     } else if (mode != 0) {
       throw ClipErr(CLIPGPU_ERR_INVALID, "bad mode");
     }
-    TCHECK(launch_gemm(dt, A_ROWS, epi, mode == 0 ? act : 0, g, nullptr));
-    TCHECK(hipDeviceSynchronize());
+    HIP_CHECK(launch_gemm(dt, A_ROWS, epi, mode == 0 ? act : 0, g, nullptr));
+    HIP_CHECK(hipDeviceSynchronize());
     if (mode == 0) down16(dt, out, dO.p, M * N);
     else if (mode == 3) down16(DT_F16, out, dO.p, M * N);
     else down(out, dO.p, M * N * 4);
@@ -172,14 +167,14 @@ int clipgpu_test_gemm_lnf(int dtype, int act, int64_t M, int64_t N, int64_t K, c
     up16(DT_F16, dW.p, wf, N * K);
     up(dB.p, bias, N * 4);
     up(dC.p, cs, N * 4);
-    TCHECK(launch_ln_stats(dA.p, 1, eps, dS.as<float>(), (int)M, (int)K, nullptr));  // the rows' (mean, rstd)
+    HIP_CHECK(launch_ln_stats(dA.p, 1, eps, dS.as<float>(), (int)M, (int)K, nullptr));  // the rows' (mean, rstd)
     GemmParams g{};
     g.tile = tile;
     g.A = dA.p; g.lda = K; g.W = dW.p; g.ldw = K; g.bias = dB.as<float>(); g.cs = dC.as<float>();
     g.rowstats = dS.as<float>();
     g.out = dO.p; g.ldo = N; g.M = (int)M; g.N = (int)N; g.K = (int)K;
-    TCHECK(launch_gemm(dt, A_ROWS, EPI_LNF, act, g, nullptr));
-    TCHECK(hipDeviceSynchronize());
+    HIP_CHECK(launch_gemm(dt, A_ROWS, EPI_LNF, act, g, nullptr));
+    HIP_CHECK(hipDeviceSynchronize());
     down16(dt, out, dO.p, M * N);
   });
 }
@@ -191,8 +186,8 @@ int clipgpu_test_attention(int dtype, int64_t B, int64_t N, int64_t H, int64_t H
     const int64_t D = H * HD;
     DevBuf dq(B * N * 3 * D * 2), dO(B * N * D * 2);
     up16(dt, dq.p, qkv, B * N * 3 * D);
-    TCHECK(launch_attention(dt, dq.p, dO.p, (int)B, (int)N, (int)H, (int)D, causal, nullptr));
-    TCHECK(hipDeviceSynchronize());
+    HIP_CHECK(launch_attention(dt, dq.p, dO.p, (int)B, (int)N, (int)H, (int)D, causal, nullptr));
+    HIP_CHECK(hipDeviceSynchronize());
     down16(dt, out, dO.p, B * N * D);
   });
 }
@@ -205,8 +200,8 @@ int clipgpu_test_layernorm(int dtype, int64_t rows, int64_t D, float eps, const 
     up(dx.p, x, rows * D * 4);
     up(dw.p, w, D * 4);
     up(db.p, b, D * 4);
-    TCHECK(launch_ln_rows(dt, dx.as<float>(), 0, dw.as<float>(), db.as<float>(), eps, dO.p, (int)rows, (int)D, nullptr));
-    TCHECK(hipDeviceSynchronize());
+    HIP_CHECK(launch_ln_rows(dt, dx.as<float>(), 0, dw.as<float>(), db.as<float>(), eps, dO.p, (int)rows, (int)D, nullptr));
+    HIP_CHECK(hipDeviceSynchronize());
     down16(dt, out, dO.p, rows * D);
   });
 }
@@ -227,7 +222,7 @@ int clipgpu_test_patch_embed(int dtype, int mode, int64_t B, int64_t S, int64_t 
     up(dpos.p, pos, tokens * D * 4);
     // the engine's stem: patch rows (16-bit) -> row GEMM with the patch epilogue
     DevBuf drows(B * G * G * Kp * 2);
-    TCHECK(launch_patch_rows(dt, mode == 0 ? A_IMG_F32 : A_IMG_U8, dpix.p, mean, stdv, drows.p, (int)B, (int)S,
+    HIP_CHECK(launch_patch_rows(dt, mode == 0 ? A_IMG_F32 : A_IMG_U8, dpix.p, mean, stdv, drows.p, (int)B, (int)S,
                              (int)P, (int)K, (int)Kp, nullptr));
     GemmParams g{};
     g.A = drows.p; g.lda = Kp;
@@ -235,8 +230,8 @@ int clipgpu_test_patch_embed(int dtype, int mode, int64_t B, int64_t S, int64_t 
     g.cls = 1;
     g.G = (int)G; g.pos = dpos.as<float>();
     g.tile = tile_override();
-    TCHECK(launch_gemm(dt, A_ROWS, EPI_PATCH, 0, g, nullptr));
-    TCHECK(hipDeviceSynchronize());
+    HIP_CHECK(launch_gemm(dt, A_ROWS, EPI_PATCH, 0, g, nullptr));
+    HIP_CHECK(hipDeviceSynchronize());
     down(x_out, dx.p, B * tokens * D * 4);
   });
 }
@@ -249,9 +244,9 @@ int clipgpu_test_patch_rows(int dtype, int mode, int64_t B, int64_t S, int64_t P
     const size_t pix_bytes = mode == 0 ? (size_t)B * 3 * S * S * 4 : (size_t)B * S * S * 3;
     DevBuf dpix(pix_bytes), drows(B * G * G * Kp * 2);
     up(dpix.p, pixels, pix_bytes);
-    TCHECK(launch_patch_rows(dt, mode == 0 ? A_IMG_F32 : A_IMG_U8, dpix.p, mean, stdv, drows.p, (int)B, (int)S,
+    HIP_CHECK(launch_patch_rows(dt, mode == 0 ? A_IMG_F32 : A_IMG_U8, dpix.p, mean, stdv, drows.p, (int)B, (int)S,
                              (int)P, (int)K, (int)Kp, nullptr));
-    TCHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipDeviceSynchronize());
     down16(dt, rows_out, drows.p, B * G * G * Kp);
   });
 }
@@ -288,8 +283,8 @@ int clipgpu_test_lane_reduce(const float* in64, float* out512) {
     DevBuf di(64 * 4), dO(512 * 4);
     up(di.p, in64, 64 * 4);
     hipLaunchKernelGGL(lane_reduce_kernel, dim3(1), dim3(64), 0, nullptr, di.as<float>(), dO.as<float>());
-    TCHECK(hipGetLastError());
-    TCHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
     down(out512, dO.p, 512 * 4);
   });
 }
@@ -299,7 +294,7 @@ int clipgpu_test_clock_probe(void* stream, int64_t duration_us, uint64_t* d_out)
     if (!d_out || duration_us <= 0 || duration_us > 10000000) throw ClipErr(CLIPGPU_ERR_INVALID, "bad clock probe");
     hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (unsigned long long*)d_out,
                        (unsigned long long)duration_us * 100ull);
-    TCHECK(hipGetLastError());
+    HIP_CHECK(hipGetLastError());
   });
 }
 
@@ -330,25 +325,25 @@ int clipgpu_test_gemm_bench_ld(int dtype, int epi, int act, int64_t M, int64_t N
     hipLaunchKernelGGL(fill_random, dim3(2048), dim3(256), 0, nullptr, fA.as<float>(), (long)(M * lda), 1u);
     hipLaunchKernelGGL(fill_random, dim3(2048), dim3(256), 0, nullptr, fW.as<float>(), (long)(N * ldw), 2u);
     hipLaunchKernelGGL(fill_random, dim3(64), dim3(256), 0, nullptr, dB.as<float>(), (long)N, 3u);
-    TCHECK(launch_cast_f32(dt, fA.as<float>(), dA.p, (long)(M * lda), nullptr));
-    TCHECK(launch_cast_f32(dt, fW.as<float>(), dW.p, (long)(N * ldw), nullptr));
-    TCHECK(hipDeviceSynchronize());
+    HIP_CHECK(launch_cast_f32(dt, fA.as<float>(), dA.p, (long)(M * lda), nullptr));
+    HIP_CHECK(launch_cast_f32(dt, fW.as<float>(), dW.p, (long)(N * ldw), nullptr));
+    HIP_CHECK(hipDeviceSynchronize());
     GemmParams g{};
     g.A = dA.p; g.lda = lda; g.W = dW.p; g.ldw = ldw; g.bias = dB.as<float>();
     g.out = dO.p; g.ldo = N; g.M = (int)M; g.N = (int)N; g.K = (int)K; g.tile = tile;
     if (tile != 0 && tile != TILE_SKINNY && !gemm_tile_built(tile)) throw ClipErr(CLIPGPU_ERR_INVALID, "not a built tile");
     const int e = (epi == 1 || epi == 3) ? EPI_RESID : (epi == 2 ? EPI_STORE32 : EPI_STORE16);
     g.x16 = epi == 3;  // the f16 residual stream (its random f32 fill read as f16: timing only)
-    for (int i = 0; i < 3; ++i) TCHECK(launch_gemm(dt, A_ROWS, e, epi == 0 ? act : 0, g, nullptr));
+    for (int i = 0; i < 3; ++i) HIP_CHECK(launch_gemm(dt, A_ROWS, e, epi == 0 ? act : 0, g, nullptr));
     hipEvent_t a, b;
-    TCHECK(hipEventCreate(&a));
-    TCHECK(hipEventCreate(&b));
-    TCHECK(hipEventRecord(a, nullptr));
-    for (int i = 0; i < iters; ++i) TCHECK(launch_gemm(dt, A_ROWS, e, epi == 0 ? act : 0, g, nullptr));
-    TCHECK(hipEventRecord(b, nullptr));
-    TCHECK(hipEventSynchronize(b));
+    HIP_CHECK(hipEventCreate(&a));
+    HIP_CHECK(hipEventCreate(&b));
+    HIP_CHECK(hipEventRecord(a, nullptr));
+    for (int i = 0; i < iters; ++i) HIP_CHECK(launch_gemm(dt, A_ROWS, e, epi == 0 ? act : 0, g, nullptr));
+    HIP_CHECK(hipEventRecord(b, nullptr));
+    HIP_CHECK(hipEventSynchronize(b));
     float ms = 0.f;
-    TCHECK(hipEventElapsedTime(&ms, a, b));
+    HIP_CHECK(hipEventElapsedTime(&ms, a, b));
     (void)hipEventDestroy(a);
     (void)hipEventDestroy(b);
     *us_per_launch = (double)ms * 1000.0 / iters;
@@ -364,19 +359,19 @@ int clipgpu_test_attention_bench(int dtype, int64_t B, int64_t N, int64_t H, int
     const int64_t D = H * HD;
     DevBuf f(B * N * 3 * D * 4), dq(B * N * 3 * D * 2), dO(B * N * D * 2);
     hipLaunchKernelGGL(fill_random, dim3(2048), dim3(256), 0, nullptr, f.as<float>(), (long)(B * N * 3 * D), 7u);
-    TCHECK(launch_cast_f32(dt, f.as<float>(), dq.p, (long)(B * N * 3 * D), nullptr));
+    HIP_CHECK(launch_cast_f32(dt, f.as<float>(), dq.p, (long)(B * N * 3 * D), nullptr));
     for (int i = 0; i < 3; ++i)
-      TCHECK(launch_attention(dt, dq.p, dO.p, (int)B, (int)N, (int)H, (int)D, causal, nullptr));
+      HIP_CHECK(launch_attention(dt, dq.p, dO.p, (int)B, (int)N, (int)H, (int)D, causal, nullptr));
     hipEvent_t a, b;
-    TCHECK(hipEventCreate(&a));
-    TCHECK(hipEventCreate(&b));
-    TCHECK(hipEventRecord(a, nullptr));
+    HIP_CHECK(hipEventCreate(&a));
+    HIP_CHECK(hipEventCreate(&b));
+    HIP_CHECK(hipEventRecord(a, nullptr));
     for (int i = 0; i < iters; ++i)
-      TCHECK(launch_attention(dt, dq.p, dO.p, (int)B, (int)N, (int)H, (int)D, causal, nullptr));
-    TCHECK(hipEventRecord(b, nullptr));
-    TCHECK(hipEventSynchronize(b));
+      HIP_CHECK(launch_attention(dt, dq.p, dO.p, (int)B, (int)N, (int)H, (int)D, causal, nullptr));
+    HIP_CHECK(hipEventRecord(b, nullptr));
+    HIP_CHECK(hipEventSynchronize(b));
     float ms = 0.f;
-    TCHECK(hipEventElapsedTime(&ms, a, b));
+    HIP_CHECK(hipEventElapsedTime(&ms, a, b));
     (void)hipEventDestroy(a);
     (void)hipEventDestroy(b);
     *us_per_launch = (double)ms * 1000.0 / iters;
@@ -388,9 +383,9 @@ int clipgpu_test_quant_rows(int64_t rows, int64_t cols, const float* in, uint8_t
     if (rows <= 0 || cols <= 0 || cols % 32) throw ClipErr(CLIPGPU_ERR_INVALID, "bad quant shape (cols % 32 == 0)");
     DevBuf dx(rows * cols * 4), dq(rows * cols), ds(rows * cols / 32);
     up(dx.p, in, rows * cols * 4);
-    TCHECK(launch_quant_rows(-1, dx.p, cols, dq.as<uint8_t>(), cols, ds.as<uint8_t>(), cols / 32, (int)rows, (int)cols,
+    HIP_CHECK(launch_quant_rows(-1, dx.p, cols, dq.as<uint8_t>(), cols, ds.as<uint8_t>(), cols / 32, (int)rows, (int)cols,
                              nullptr));
-    TCHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipDeviceSynchronize());
     down(q, dq.p, rows * cols);
     down(qs, ds.p, rows * cols / 32);
   });
@@ -404,9 +399,9 @@ int clipgpu_test_layernorm_mx(int64_t rows, int64_t D, float eps, const float* x
     up(dx.p, x, rows * D * 4);
     up(dw.p, w, D * 4);
     up(db.p, b, D * 4);
-    TCHECK(launch_ln_rows(DT_BF16, dx.as<float>(), 0, dw.as<float>(), db.as<float>(), eps, dq.p, (int)rows, (int)D,
+    HIP_CHECK(launch_ln_rows(DT_BF16, dx.as<float>(), 0, dw.as<float>(), db.as<float>(), eps, dq.p, (int)rows, (int)D,
                           nullptr, ds.as<uint8_t>()));
-    TCHECK(hipDeviceSynchronize());
+    HIP_CHECK(hipDeviceSynchronize());
     down(q, dq.p, rows * D);
     down(qs, ds.p, rows * D / 32);
   });
@@ -438,8 +433,8 @@ int clipgpu_test_gemm_mx(int dtype, int mode, int act, int64_t M, int64_t N, int
       g.ldos = N / 32;
     }
     if (epi == EPI_RESID && resid) up(dO.p, resid, M * N * 4);
-    TCHECK(launch_gemm_mx(dt, epi, (epi == EPI_STORE16 || epi == EPI_STOREQ) ? act : 0, g, nullptr));
-    TCHECK(hipDeviceSynchronize());
+    HIP_CHECK(launch_gemm_mx(dt, epi, (epi == EPI_STORE16 || epi == EPI_STOREQ) ? act : 0, g, nullptr));
+    HIP_CHECK(hipDeviceSynchronize());
     if (epi == EPI_STORE16) down16(dt, out, dO.p, M * N);
     else if (epi == EPI_STOREQ) {
       down(outq, dO.p, M * N);
@@ -458,9 +453,9 @@ int clipgpu_test_gemm_mx_bench(int epi, int act, int64_t M, int64_t N, int64_t K
     hipLaunchKernelGGL(fill_random, dim3(2048), dim3(256), 0, nullptr, fA.as<float>(), (long)(M * K), 1u);
     hipLaunchKernelGGL(fill_random, dim3(2048), dim3(256), 0, nullptr, fW.as<float>(), (long)(N * K), 2u);
     hipLaunchKernelGGL(fill_random, dim3(64), dim3(256), 0, nullptr, dB.as<float>(), (long)N, 3u);
-    TCHECK(launch_quant_rows(-1, fA.p, K, dA.as<uint8_t>(), K, dAs.as<uint8_t>(), K / 32, (int)M, (int)K, nullptr));
-    TCHECK(launch_quant_rows(-1, fW.p, K, dW.as<uint8_t>(), K, dWs.as<uint8_t>(), K / 32, (int)N, (int)K, nullptr));
-    TCHECK(hipDeviceSynchronize());
+    HIP_CHECK(launch_quant_rows(-1, fA.p, K, dA.as<uint8_t>(), K, dAs.as<uint8_t>(), K / 32, (int)M, (int)K, nullptr));
+    HIP_CHECK(launch_quant_rows(-1, fW.p, K, dW.as<uint8_t>(), K, dWs.as<uint8_t>(), K / 32, (int)N, (int)K, nullptr));
+    HIP_CHECK(hipDeviceSynchronize());
     MxGemmParams g{};
     g.A = dA.as<uint8_t>(); g.lda = K; g.As = dAs.as<uint8_t>(); g.ldas = K / 32;
     g.W = dW.as<uint8_t>(); g.ldw = K; g.Ws = dWs.as<uint8_t>(); g.ldws = K / 32;
@@ -472,16 +467,16 @@ int clipgpu_test_gemm_mx_bench(int epi, int act, int64_t M, int64_t N, int64_t K
       g.ldos = N / 32;
     }
     const int a = (e == EPI_STORE16 || e == EPI_STOREQ) ? act : 0;
-    for (int i = 0; i < 3; ++i) TCHECK(launch_gemm_mx(DT_BF16, e, a, g, nullptr));
+    for (int i = 0; i < 3; ++i) HIP_CHECK(launch_gemm_mx(DT_BF16, e, a, g, nullptr));
     hipEvent_t ea, eb;
-    TCHECK(hipEventCreate(&ea));
-    TCHECK(hipEventCreate(&eb));
-    TCHECK(hipEventRecord(ea, nullptr));
-    for (int i = 0; i < iters; ++i) TCHECK(launch_gemm_mx(DT_BF16, e, a, g, nullptr));
-    TCHECK(hipEventRecord(eb, nullptr));
-    TCHECK(hipEventSynchronize(eb));
+    HIP_CHECK(hipEventCreate(&ea));
+    HIP_CHECK(hipEventCreate(&eb));
+    HIP_CHECK(hipEventRecord(ea, nullptr));
+    for (int i = 0; i < iters; ++i) HIP_CHECK(launch_gemm_mx(DT_BF16, e, a, g, nullptr));
+    HIP_CHECK(hipEventRecord(eb, nullptr));
+    HIP_CHECK(hipEventSynchronize(eb));
     float ms = 0.f;
-    TCHECK(hipEventElapsedTime(&ms, ea, eb));
+    HIP_CHECK(hipEventElapsedTime(&ms, ea, eb));
     (void)hipEventDestroy(ea);
     (void)hipEventDestroy(eb);
     *us_per_launch = (double)ms * 1000.0 / iters;
@@ -535,7 +530,7 @@ int clipgpu_test_host_copy(int64_t bytes, int mode, int iters, double* us_per_co
     if (posix_memalign(&src, 4096, (size_t)bytes) != 0) throw ClipErr(CLIPGPU_ERR_INVALID, "host alloc");
     std::memset(src, 3, (size_t)bytes);
     void* dst = nullptr;
-    if (mode >= 2) TCHECK(hipHostMalloc(&dst, (size_t)bytes, hipHostMallocDefault));
+    if (mode >= 2) HIP_CHECK(hipHostMalloc(&dst, (size_t)bytes, hipHostMallocDefault));
     else if (posix_memalign(&dst, 4096, (size_t)bytes) != 0) throw ClipErr(CLIPGPU_ERR_INVALID, "host alloc");
     std::memset(dst, 0, (size_t)bytes);
     auto once = [&]() {
@@ -562,14 +557,14 @@ int clipgpu_test_h2d_bench(int64_t bytes, int mode, int iters, double* us_per_co
     // src 0: hipHostMalloc; 1: page-aligned malloc'd memory registered as clipgpu_host_register does
     void* host = nullptr;
     if (src == 0) {
-      TCHECK(hipHostMalloc(&host, (size_t)bytes, hipHostMallocMapped | hipHostMallocPortable));
+      HIP_CHECK(hipHostMalloc(&host, (size_t)bytes, hipHostMallocMapped | hipHostMallocPortable));
     } else {
       if (posix_memalign(&host, 4096, (size_t)bytes) != 0) throw ClipErr(CLIPGPU_ERR_INVALID, "host alloc");
       std::memset(host, 1, (size_t)bytes);
       const hipError_t e = hipHostRegister(host, (size_t)bytes, hipHostRegisterMapped | hipHostRegisterPortable);
       if (e != hipSuccess) {
         std::free(host);
-        TCHECK(e);
+        HIP_CHECK(e);
       }
     }
     std::memset(host, 1, (size_t)bytes);
@@ -580,33 +575,33 @@ int clipgpu_test_h2d_bench(int64_t bytes, int mode, int iters, double* us_per_co
     auto run = [&]() {
       const size_t h = (size_t)bytes / 2;
       switch (mode) {
-        case 0: TCHECK(hipMemcpyAsync(dst.p, host, (size_t)bytes, hipMemcpyHostToDevice, s0)); break;
-        case 1: TCHECK(launch_pull_copy(mapped, dst.p, (size_t)bytes, s0)); break;
+        case 0: HIP_CHECK(hipMemcpyAsync(dst.p, host, (size_t)bytes, hipMemcpyHostToDevice, s0)); break;
+        case 1: HIP_CHECK(launch_pull_copy(mapped, dst.p, (size_t)bytes, s0)); break;
         default:  // halves on two streams: 2 = two SDMA copies, 3 = the pull kernel beside one SDMA copy
-          TCHECK(hipEventRecord(j, s0));
-          TCHECK(hipStreamWaitEvent(s1, j, 0));
-          if (mode == 2) TCHECK(hipMemcpyAsync(dst.p, host, h, hipMemcpyHostToDevice, s0));
-          else TCHECK(launch_pull_copy(mapped, dst.p, h, s0));
-          TCHECK(hipMemcpyAsync((char*)dst.p + h, (char*)host + h, (size_t)bytes - h, hipMemcpyHostToDevice, s1));
-          TCHECK(hipEventRecord(j, s1));
-          TCHECK(hipStreamWaitEvent(s0, j, 0));
+          HIP_CHECK(hipEventRecord(j, s0));
+          HIP_CHECK(hipStreamWaitEvent(s1, j, 0));
+          if (mode == 2) HIP_CHECK(hipMemcpyAsync(dst.p, host, h, hipMemcpyHostToDevice, s0));
+          else HIP_CHECK(launch_pull_copy(mapped, dst.p, h, s0));
+          HIP_CHECK(hipMemcpyAsync((char*)dst.p + h, (char*)host + h, (size_t)bytes - h, hipMemcpyHostToDevice, s1));
+          HIP_CHECK(hipEventRecord(j, s1));
+          HIP_CHECK(hipStreamWaitEvent(s0, j, 0));
       }
     };
     std::exception_ptr err;
     try {
-      TCHECK(hipHostGetDevicePointer(&mapped, host, 0));
-      TCHECK(hipStreamCreateWithFlags(&s0, hipStreamNonBlocking));
-      TCHECK(hipStreamCreateWithFlags(&s1, hipStreamNonBlocking));
-      TCHECK(hipEventCreate(&a));
-      TCHECK(hipEventCreate(&b));
-      TCHECK(hipEventCreateWithFlags(&j, hipEventDisableTiming));
+      HIP_CHECK(hipHostGetDevicePointer(&mapped, host, 0));
+      HIP_CHECK(hipStreamCreateWithFlags(&s0, hipStreamNonBlocking));
+      HIP_CHECK(hipStreamCreateWithFlags(&s1, hipStreamNonBlocking));
+      HIP_CHECK(hipEventCreate(&a));
+      HIP_CHECK(hipEventCreate(&b));
+      HIP_CHECK(hipEventCreateWithFlags(&j, hipEventDisableTiming));
       for (int i = 0; i < 3; ++i) run();
-      TCHECK(hipEventRecord(a, s0));
+      HIP_CHECK(hipEventRecord(a, s0));
       for (int i = 0; i < iters; ++i) run();
-      TCHECK(hipEventRecord(b, s0));
-      TCHECK(hipEventSynchronize(b));
+      HIP_CHECK(hipEventRecord(b, s0));
+      HIP_CHECK(hipEventSynchronize(b));
       float ms = 0.f;
-      TCHECK(hipEventElapsedTime(&ms, a, b));
+      HIP_CHECK(hipEventElapsedTime(&ms, a, b));
       *us_per_copy = (double)ms * 1000.0 / iters;
     } catch (...) {
       err = std::current_exception();
@@ -638,19 +633,19 @@ int clipgpu_diag_gemm_stamps(int dtype, int epi, int act, int64_t M, int64_t N, 
     hipLaunchKernelGGL(fill_random, dim3(2048), dim3(256), 0, nullptr, fA.as<float>(), (long)(M * K), 1u);
     hipLaunchKernelGGL(fill_random, dim3(2048), dim3(256), 0, nullptr, fW.as<float>(), (long)(N * K), 2u);
     hipLaunchKernelGGL(fill_random, dim3(64), dim3(256), 0, nullptr, dB.as<float>(), (long)N, 3u);
-    TCHECK(launch_cast_f32(dt, fA.as<float>(), dA.p, (long)(M * K), nullptr));
-    TCHECK(launch_cast_f32(dt, fW.as<float>(), dW.p, (long)(N * K), nullptr));
+    HIP_CHECK(launch_cast_f32(dt, fA.as<float>(), dA.p, (long)(M * K), nullptr));
+    HIP_CHECK(launch_cast_f32(dt, fW.as<float>(), dW.p, (long)(N * K), nullptr));
     GemmParams g{};
     g.A = dA.p; g.lda = K; g.W = dW.p; g.ldw = K; g.bias = dB.as<float>();
     g.out = dO.p; g.ldo = N; g.M = (int)M; g.N = (int)N; g.K = (int)K; g.tile = tile; g.diag = diag;
     const int e = (epi == 1 || epi == 3) ? EPI_RESID : (epi == 2 ? EPI_STORE32 : EPI_STORE16);
     g.x16 = epi == 3;  // the f16 residual stream (timing only)
-    for (int i = 0; i < 20; ++i) TCHECK(launch_gemm(dt, A_ROWS, e, epi == 0 ? act : 0, g, nullptr));
-    TCHECK(hipDeviceSynchronize());
-    TCHECK(read_gemm_stamps(nullptr, nblocks, true));
-    TCHECK(launch_gemm(dt, A_ROWS, e, epi == 0 ? act : 0, g, nullptr));
-    TCHECK(hipDeviceSynchronize());
-    TCHECK(read_gemm_stamps(out, nblocks, false));
+    for (int i = 0; i < 20; ++i) HIP_CHECK(launch_gemm(dt, A_ROWS, e, epi == 0 ? act : 0, g, nullptr));
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(read_gemm_stamps(nullptr, nblocks, true));
+    HIP_CHECK(launch_gemm(dt, A_ROWS, e, epi == 0 ? act : 0, g, nullptr));
+    HIP_CHECK(hipDeviceSynchronize());
+    HIP_CHECK(read_gemm_stamps(out, nblocks, false));
   });
 }
 

@@ -70,7 +70,7 @@ const char* clipgpu_build_source_hash(void);
  * batch sharding across them); NULL/0 = device 0.  max_batch: rows per device per launch
  * (larger batches are processed in chunks).
  * Speed (never the output bits): the GEMM tiles and lane count come from a table measured on
- * MI355X (engine.hip table_tiles / table_lanes) for one lane's token rows at max_batch: the
+ * MI355X (engine/tiles.hip table_tiles / table_lanes) for one lane's token rows at max_batch: the
  * measured regimes are >= 2048 rows per lane (ViT-B/32 vision 256, text 1024, SO400M 128, H/14
  * 64 per GPU); smaller max_batch uses the shape heuristic (skinny kernel at <= 256 rows), and
  * clipgpu_options.tuning = 1 times the candidates at creation for any other batch. */

@@ -294,7 +294,7 @@ def test_options_init_and_validation():
                                             ([1000, 1000, 1000], [0, 1000, 2000, 3000], 1),
                                             ([5], [0, 5], 1)])
 def test_gather_plan(rows, off, equal):
-    """The gathered entry points' host-side plan (engine.hip plan_gather): rank-order offsets of
+    """The gathered entry points' host-side plan (engine/gather.hip plan_gather): rank-order offsets of
     every rank's block, and the all-gather (equal blocks) vs one-broadcast-per-block choice, incl.
     zero-row ranks and blocks larger than max_batch (chunked per rank; offsets are per rank)."""
     from open_clip_inference import _lib

@@ -337,7 +337,7 @@ def test_rccl_communicator_and_gathered_entry_points(monkeypatch):
 
 def test_multi_round_host_calls_alternate_buffer_sets_bit_exactly():
     """A host-buffer call of more than max_batch rows runs its rounds on two alternating staging sets
-    (engine.hip run_host_shard: round i + 1's H2D under round i's forward).  Every
+    (engine/host_path.hip run_host_shard: round i + 1's H2D under round i's forward).  Every
     round must equal the same rows embedded by a call of their own, bit for bit: u8 and f32 pixels
     and token ids, pageable and caller-registered buffers, a ragged last round, and a second
     multi-round call (graph replay on both sets).  The staging copies run on the persistent copy pool
@@ -439,7 +439,7 @@ def test_one_device_clique_runs_the_multi_device_comm_path():
 
 
 def test_tile_table_is_deterministic_and_bit_invisible():
-    """The default tile choice is the committed table (engine.hip table_tiles): two engines of
+    """The default tile choice is the committed table (engine/tiles.hip table_tiles): two engines of
     the bench's configuration pick the same tiles and lanes on any box (vision at 256 images: two
     lanes, qkv / c_fc / c_proj on the 4-wave 160x128 RS tile, out_proj on the 8-wave 224x192); a timing tuner
     (clipgpu_options.tuning) may pick others, with the same output bits."""
@@ -472,6 +472,43 @@ def test_tile_table_is_deterministic_and_bit_invisible():
     ids[:, 0] = 49406
     ids[np.arange(8), rng.integers(5, 77, size=8)] = 49407
     assert np.array_equal(ta.embed_tokens(ids), ts.embed_tokens(ids))
+
+
+def test_failed_create_releases_its_device_memory():
+    """A clipgpu_create that fails after its first device allocation releases what it had allocated
+    (engine/api.hip destroy_engine).  max_batch = 2^22 asks for a workspace of ~645 GB for the ViT-B/32
+    residual stream alone: hipMalloc refuses it at once, after the weight arena is uploaded, and nothing is
+    launched on it.  The call returns CLIPGPU_ERR_DEVICE, the device's free memory drops by less than half
+    of the tower's 16-bit weight bytes (a leaked arena is at least all of them), and the next engine on
+    the device computes the same bits as one created before the failure."""
+    import ctypes
+    import torch
+    from oracle.model_spec import VIT_B_32_CFG
+    from open_clip_inference import _lib
+    from open_clip_inference.engine import Engine
+    from open_clip_inference.error import InferenceError
+    from tests.helpers import normalized_pixels
+    d = make_model_dir(VIT_B_32_CFG, seed=1234)
+    v = vision_spec_from_cfg(VIT_B_32_CFG["model_cfg"])
+    x = normalized_pixels(weights.synth_images_u8(17, 8, v.image_size), OPENAI_MEAN, OPENAI_STD)
+    fresh = Engine(d, 0, [0], "bf16", 8)
+    ref = fresh.embed_pixels(x)
+    fresh.close()
+    weight_bytes = 2 * sum(int(np.prod(shape)) for _, shape, _, _ in weights.vision_param_list(v))
+    torch.cuda.synchronize()
+    free_before = torch.cuda.mem_get_info(0)[0]
+    h = ctypes.c_void_p()
+    rc = _lib.lib().clipgpu_create(d.encode(), 0, (ctypes.c_int * 1)(0), 1, _lib.DTYPE_BF16, 1 << 22, ctypes.byref(h))
+    assert rc == 4 and not h.value  # CLIPGPU_ERR_DEVICE
+    with pytest.raises(InferenceError):
+        _lib.check(rc)
+    torch.cuda.synchronize()
+    free_after = torch.cuda.mem_get_info(0)[0]
+    print(f"free before {free_before} after {free_after} drop {free_before - free_after} weight bytes {weight_bytes}")
+    assert free_before - free_after < weight_bytes // 2
+    again = Engine(d, 0, [0], "bf16", 8)
+    assert np.array_equal(again.embed_pixels(x), ref)
+    again.close()
 
 
 def test_siglip2_text_embedder_and_clip_end_to_end():

@@ -393,7 +393,7 @@ def test_concurrent_lanes_are_bit_exact(tower):
 @pytest.mark.parametrize("tower", [0, 1])
 def test_last_layer_pruning_is_bit_exact(cfg, dtype, tower):
     """The last layer run on the pooled rows only (CLS / EOT argmax gathered after attention,
-    engine.hip trunk) gives the same bits as the full last layer: every op after attention is
+    engine/forward.hip trunk) gives the same bits as the full last layer: every op after attention is
     row-local and each kept row goes through the same kernels.  Random EOT positions, two
     lanes, and a batch whose rows-per-lane exceed the token count (gather sources and
     destinations interleave)."""

@@ -23,7 +23,7 @@ lib.clipgpu_last_error.restype = ctypes.c_char_p
 NB = 2048
 
 # (name, epi (0 store16, 1 residual f32, 3 residual f16), act, M, N, K, tile): the committed table's
-# tiles (engine.hip table_tiles) at the bench's two-lane rows (6400 per lane) and at one lane's 12800
+# tiles (engine/tiles.hip table_tiles) at the bench's two-lane rows (6400 per lane) and at one lane's 12800
 CASES = [
     ("t26_c_proj 224x192w8", 3, 0, 6400, 768, 3072, 26),
     ("t26_out 224x192w8", 3, 0, 6400, 768, 768, 26),

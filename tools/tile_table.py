@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Regenerate / check the committed tile table (engine.hip table_tiles) on one MI355X.
+"""Regenerate / check the committed tile table (engine/tiles.hip table_tiles) on one MI355X.
 
 For each BASELINE workload (per-GPU batch), builds engines with
   * the committed table (lanes = 1, the default),
