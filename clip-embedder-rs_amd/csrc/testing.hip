@@ -94,9 +94,209 @@ void down16(DType dt, float* h, const void* d16, size_t n) {
   down(h, tmp.p, n * 4);
 }
 
+// Status of a row / MAP launcher in the hooks below: its own refusal (hipErrorInvalidValue, returned
+// before anything is launched) is the caller's bad shape -> CLIPGPU_ERR_INVALID, so the tests can check
+// the refusals; anything else is a device error.
+void launched(hipError_t e, const char* what) {
+  if (e == hipErrorInvalidValue) {
+    (void)hipGetLastError();
+    throw ClipErr(CLIPGPU_ERR_INVALID, std::string(what) + ": refused (hipErrorInvalidValue)");
+  }
+  check(e, what);
+}
+
+// A residual-stream buffer of n elements from host f32: f32, or f16 (x16) -- and back, widened exactly.
+void up_stream(int x16, void* d, const float* h, size_t n) {
+  if (x16) up16(DT_F16, d, h, n);
+  else up(d, h, n * 4);
+}
+void down_stream(int x16, float* h, const void* d, size_t n) {
+  if (x16) down16(DT_F16, h, d, n);
+  else down(h, d, n * 4);
+}
+
+void require(bool ok, const char* msg) {
+  if (!ok) throw ClipErr(CLIPGPU_ERR_INVALID, msg);
+}
+
 }  // namespace
 
 extern "C" {
+
+int clipgpu_test_ln_rows(int dtype, int x16, int64_t rows, int64_t D, float eps, const float* x, const float* w,
+                         const float* b, float* out, float* stats, uint8_t* q, uint8_t* qs) {
+  return guarded([&]() {
+    const DType dt = dt_of(dtype);
+    require(rows > 0 && D > 0 && rows * D < INT32_MAX && x && w && b && out && stats && (q == nullptr) == (qs == nullptr),
+            "bad LN arguments");
+    DevBuf dx(rows * D * 4), dw(D * 4), db(D * 4), dO(rows * D * 2), dS(rows * 8), dq(rows * D), ds(rows * (D / 32 + 1));
+    up_stream(x16, dx.p, x, rows * D);
+    up(dw.p, w, D * 4);
+    up(db.p, b, D * 4);
+    if (qs != nullptr)  // first: its refusal (D % 32) comes before any launch
+      launched(launch_ln_rows(dt, dx.p, x16, dw.as<float>(), db.as<float>(), eps, dq.p, (int)rows, (int)D, nullptr,
+                              ds.as<uint8_t>()),
+               "launch_ln_rows (MX)");
+    launched(launch_ln_rows(dt, dx.p, x16, dw.as<float>(), db.as<float>(), eps, dO.p, (int)rows, (int)D, nullptr),
+             "launch_ln_rows");
+    launched(launch_ln_stats(dx.p, x16, eps, dS.as<float>(), (int)rows, (int)D, nullptr), "launch_ln_stats");
+    HIP_CHECK(hipDeviceSynchronize());
+    down16(dt, out, dO.p, rows * D);
+    down(stats, dS.p, rows * 8);
+    if (qs != nullptr) {
+      down(q, dq.p, rows * D);
+      down(qs, ds.p, rows * (D / 32));
+    }
+  });
+}
+
+}  // extern "C"
+
+namespace {
+// What a stem hook returns beside the stream: mode 0 h as 16-bit, 1 ln_1's statistics only (h == nullptr),
+// 2 h as MX-fp8.  The launch itself is `go(h, qs, stats)`.
+template <typename Go>
+void run_stem(DType dt, int x16, int mode, int64_t rows, int64_t D, const void* dx, Go go, const char* what,
+              float* x_out, float* h_out, float* stats_out, uint8_t* q_out, uint8_t* qs_out) {
+  require(mode >= 0 && mode <= 2 && x_out, "bad stem mode");
+  require(mode == 0 ? h_out != nullptr : mode == 1 ? stats_out != nullptr : (q_out && qs_out), "missing stem output");
+  DevBuf dH(rows * D * 2), dS(rows * 8), ds(rows * (D / 32 + 1));
+  launched(go(mode == 1 ? nullptr : dH.p, mode == 2 ? ds.as<uint8_t>() : nullptr, mode == 1 ? dS.as<float>() : nullptr),
+           what);
+  HIP_CHECK(hipDeviceSynchronize());
+  down_stream(x16, x_out, dx, rows * D);
+  if (mode == 0) down16(dt, h_out, dH.p, rows * D);
+  if (mode == 1) down(stats_out, dS.p, rows * 8);
+  if (mode == 2) {
+    down(q_out, dH.p, rows * D);
+    down(qs_out, ds.p, rows * (D / 32));
+  }
+}
+}  // namespace
+
+extern "C" {
+
+int clipgpu_test_vision_stem(int dtype, int x16, int mode, int64_t B, int64_t tokens, int64_t D, float eps,
+                             const float* x_in, const float* cls, const float* pos, const float* lnpre_w,
+                             const float* lnpre_b, const float* ln1_w, const float* ln1_b, float* x_out, float* h_out,
+                             float* stats_out, uint8_t* q_out, uint8_t* qs_out) {
+  return guarded([&]() {
+    const DType dt = dt_of(dtype);
+    require(B > 0 && tokens > 0 && D > 0 && B * tokens * D < INT32_MAX, "bad stem shape");
+    const int64_t rows = B * tokens;
+    DevBuf dx(rows * D * 4), dc(D * 4), dp(D * 4), g0(D * 4), b0(D * 4), g1(D * 4), b1(D * 4);
+    up_stream(x16, dx.p, x_in, rows * D);
+    const float* hs[6] = {cls, pos, lnpre_w, lnpre_b, ln1_w, ln1_b};
+    DevBuf* dev[6] = {&dc, &dp, &g0, &b0, &g1, &b1};
+    for (int i = 0; i < 6; ++i) up(dev[i]->p, hs[i], D * 4);
+    run_stem(dt, x16, mode, rows, D, dx.p,
+             [&](void* h, uint8_t* qs, float* stats) {
+               return launch_vision_embed_ln(dt, dx.p, x16, dc.as<float>(), dp.as<float>(), g0.as<float>(),
+                                             b0.as<float>(), g1.as<float>(), b1.as<float>(), eps, h, (int)B,
+                                             (int)tokens, (int)D, nullptr, qs, stats);
+             },
+             "launch_vision_embed_ln", x_out, h_out, stats_out, q_out, qs_out);
+  });
+}
+
+int clipgpu_test_text_stem(int dtype, int x16, int mode, int64_t B, int64_t T, int64_t D, int64_t vocab, int64_t npos,
+                           float eps, const int64_t* ids, const float* tok, const float* pos, const float* ln1_w,
+                           const float* ln1_b, float* x_out, float* h_out, float* stats_out, uint8_t* q_out,
+                           uint8_t* qs_out) {
+  return guarded([&]() {
+    const DType dt = dt_of(dtype);
+    require(B > 0 && T > 0 && D > 0 && vocab > 0 && npos >= T && B * T * D < INT32_MAX && vocab * D < INT32_MAX,
+            "bad stem shape");
+    const int64_t rows = B * T;
+    DevBuf dx(rows * D * 4), di(rows * 8), dtok(vocab * D * 4), dp(npos * D * 4), g1(D * 4), b1(D * 4);
+    up(di.p, ids, rows * 8);
+    up(dtok.p, tok, vocab * D * 4);
+    up(dp.p, pos, npos * D * 4);
+    up(g1.p, ln1_w, D * 4);
+    up(b1.p, ln1_b, D * 4);
+    run_stem(dt, x16, mode, rows, D, dx.p,
+             [&](void* h, uint8_t* qs, float* stats) {
+               return launch_text_embed_ln(dt, di.as<int64_t>(), dtok.as<float>(), dp.as<float>(), g1.as<float>(),
+                                           b1.as<float>(), eps, dx.p, x16, h, (int)B, (int)T, (int)D, (int)vocab,
+                                           nullptr, qs, stats);
+             },
+             "launch_text_embed_ln", x_out, h_out, stats_out, q_out, qs_out);
+  });
+}
+
+int clipgpu_test_pool(int dtype, int x16, int64_t B, int64_t tokens, int64_t D, const float* x, const uint16_t* h16_bits,
+                      const int64_t* ids, const float* w, const float* b, float eps, float* pooled_out,
+                      void* xc_out_bits, uint16_t* hc_out_bits) {
+  return guarded([&]() {
+    const DType dt = dt_of(dtype);
+    require(B > 0 && tokens > 0 && D > 0 && B * tokens * D < INT32_MAX && x, "bad pool shape");
+    require((xc_out_bits == nullptr) == (hc_out_bits == nullptr) && (hc_out_bits == nullptr) == (h16_bits == nullptr) &&
+                (pooled_out || xc_out_bits) && (!pooled_out || (w && b)),
+            "bad pool arguments");
+    const int64_t rows = B * tokens, xb = x16 ? 2 : 4;
+    DevBuf dx(rows * D * 4), dh(rows * D * 2), di(rows * 8), dw(D * 4), db(D * 4), dP(B * D * 2), dxc(B * D * 4),
+        dhc(B * D * 2);
+    up_stream(x16, dx.p, x, rows * D);
+    if (ids) up(di.p, ids, rows * 8);
+    const int64_t* dids = ids ? di.as<int64_t>() : nullptr;
+    if (pooled_out) {
+      up(dw.p, w, D * 4);
+      up(db.p, b, D * 4);
+      launched(launch_pool_ln(dt, dx.p, x16, dids, (int)tokens, dw.as<float>(), db.as<float>(), eps, dP.p, (int)B,
+                              (int)D, nullptr),
+               "launch_pool_ln");
+    }
+    if (xc_out_bits) {
+      up(dh.p, h16_bits, rows * D * 2);
+      launched(launch_gather_pooled(dx.p, x16, dh.p, dids, (int)tokens, dxc.p, dhc.p, (int)B, (int)D, nullptr),
+               "launch_gather_pooled");
+    }
+    HIP_CHECK(hipDeviceSynchronize());
+    if (pooled_out) down16(dt, pooled_out, dP.p, B * D);
+    if (xc_out_bits) {
+      down(xc_out_bits, dxc.p, B * D * xb);
+      down(hc_out_bits, dhc.p, B * D * 2);
+    }
+  });
+}
+
+int clipgpu_test_map_attention(int dtype, int64_t B, int64_t N, int64_t H, int64_t D, const float* q, const float* kv,
+                               float* out) {
+  return guarded([&]() {
+    const DType dt = dt_of(dtype);
+    require(B > 0 && N > 0 && H > 0 && D > 0 && B * N * 2 * D < INT32_MAX && q && kv && out, "bad MAP arguments");
+    DevBuf dq(D * 4), dkv(B * N * 2 * D * 2), dO(B * D * 2);
+    up(dq.p, q, D * 4);
+    up16(dt, dkv.p, kv, B * N * 2 * D);
+    launched(launch_map_attention(dt, dq.as<float>(), dkv.p, dO.p, (int)B, (int)N, (int)H, (int)D, nullptr),
+             "launch_map_attention");
+    HIP_CHECK(hipDeviceSynchronize());
+    down16(dt, out, dO.p, B * D);
+  });
+}
+
+int clipgpu_test_l2norm(int64_t B, int64_t E, const float* in, float* out) {
+  return guarded([&]() {
+    require(B > 0 && E > 0 && B * E < INT32_MAX && in && out, "bad l2norm arguments");
+    DevBuf di(B * E * 4), dO(B * E * 4);
+    up(di.p, in, B * E * 4);
+    launched(launch_l2norm(di.as<float>(), dO.as<float>(), (int)B, (int)E, nullptr), "launch_l2norm");
+    HIP_CHECK(hipDeviceSynchronize());
+    down(out, dO.p, B * E * 4);
+  });
+}
+
+int clipgpu_test_cast(int dtype, int64_t n, const float* in, float* out) {
+  return guarded([&]() {
+    const DType dt = dt_of(dtype);
+    require(n > 0 && in && out, "bad cast arguments");
+    DevBuf di(n * 4), dO(n * 2);
+    up(di.p, in, n * 4);
+    launched(launch_cast_f32(dt, di.as<float>(), dO.p, (long)n, nullptr), "launch_cast_f32");
+    HIP_CHECK(hipDeviceSynchronize());
+    down16(dt, out, dO.p, n);
+  });
+}
 
 int clipgpu_test_gemm(int dtype, int mode, int act, int64_t M, int64_t N, int64_t K, const float* A, const float* W,
                       const float* bias, const float* resid, float* out) {

@@ -83,6 +83,15 @@ _PROTOS = [
                                c_void_p, c_float, c_int, c_void_p]),
     ("clipgpu_test_attention", c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p]),
     ("clipgpu_test_layernorm", c_int, [c_int, c_int64, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("clipgpu_test_ln_rows", c_int, [c_int, c_int, c_int64, c_int64, c_float] + [c_void_p] * 7),
+    ("clipgpu_test_vision_stem", c_int, [c_int, c_int, c_int, c_int64, c_int64, c_int64, c_float] + [c_void_p] * 12),
+    ("clipgpu_test_text_stem", c_int, [c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_float]
+                                      + [c_void_p] * 10),
+    ("clipgpu_test_pool", c_int, [c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    ("clipgpu_test_map_attention", c_int, [c_int, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    ("clipgpu_test_l2norm", c_int, [c_int64, c_int64, c_void_p, c_void_p]),
+    ("clipgpu_test_cast", c_int, [c_int, c_int64, c_void_p, c_void_p]),
     ("clipgpu_test_gemm_grid", c_int, [c_int, c_int64, c_int64, c_int64, POINTER(c_int)]),
     ("clipgpu_test_gemm_bench", c_int, [c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int, c_int, POINTER(c_double)]),
     ("clipgpu_test_h2d_bench", c_int, [c_int64, c_int, c_int, POINTER(c_double)]),

@@ -5,6 +5,23 @@
  * device 0, and copies the result back, so tests/ can check every kernel in
  * isolation against a numpy fp32/fp64 reference of the same op.  All return 0 on
  * success (message via clipgpu_last_error()).  dtype: CLIPGPU_DTYPE_BF16 / _F16.
+ *
+ * Tolerances of the row-kernel and MAP hooks (tests/test_gpu_rowwise.py), against fp64 numpy on
+ * the inputs as the kernel sees them (f32, or pre-rounded to the 16-bit type):
+ *   - A wave's row reduction is at most 20 per-lane adds plus 6 shuffle levels; with the divide,
+ *     subtract, multiply and fma every f32 result carries fewer than 64 roundings of 2^-24.
+ *   - f32 LayerNorm outputs (the vision stem's stream):
+ *       f32bound = 64 * 2^-24 * (|ref| + |gamma| * rstd * mean|x_row| + |beta|)
+ *     (the middle term carries the error of the mean, which is relative to |x|, not to x - mean).
+ *   - statistics: |mean - ref| <= 64 * 2^-24 * mean|x_row|, |rstd / ref - 1| <= 64 * 2^-24.
+ *   - 16-bit LayerNorm outputs: 1.01 * rel * |ref| + f32bound, rel = 2^-8 (bf16) / 2^-11 (f16):
+ *     one output rounding on top of the f32 result.
+ *   - an f16 stream is normalised as stored: the reference rounds the stored row to f16 first.
+ *   - MAP attention: 1.01 * rel * |ref| + 1e-4 * max|v| (one output rounding plus the absolute
+ *     slack the GEMM tests grant f32 accumulation; the probabilities stay in f32).
+ *   - l2norm: 32 * 2^-24 * |ref|;  gathers, stem sums, casts and MX bytes: bit for bit.
+ * A launcher's own refusal (hipErrorInvalidValue, before anything is launched) comes back from these
+ * hooks as CLIPGPU_ERR_INVALID.
  */
 #ifndef CLIPGPU_TESTING_H
 #define CLIPGPU_TESTING_H
@@ -42,6 +59,46 @@ int clipgpu_test_attention(int dtype, int64_t B, int64_t N, int64_t H, int64_t H
 /* out[r] = LN(x[r]) (16-bit output returned as f32). */
 int clipgpu_test_layernorm(int dtype, int64_t rows, int64_t D, float eps, const float* x, const float* w,
                            const float* b, float* out);
+
+/* launch_ln_rows and launch_ln_stats on one device buffer: x [rows][D] uploaded as f32, or as f16
+ * (x16, the f16 residual stream; pass values that are exact in f16).  out = LN(x) in dtype, widened to
+ * f32; stats [rows][2] = the f32 (mean, rstd) the LayerNorm-folded GEMMs read.  q / qs (both or
+ * neither): also the MX-fp8 output, q [rows][D], qs [rows][D/32] (refused unless D % 32 == 0). */
+int clipgpu_test_ln_rows(int dtype, int x16, int64_t rows, int64_t D, float eps, const float* x, const float* w,
+                         const float* b, float* out, float* stats, uint8_t* q, uint8_t* qs);
+
+/* Vision stem (launch_vision_embed_ln) on a stream x_in [B*tokens][D] (f32, or f16 when x16) whose
+ * rows r % tokens == 0 are replaced by cls + pos (cls, pos: [D], positional row 0): x_out = the stream
+ * after the kernel (ln_pre of every row), widened exactly to f32.  mode 0: h_out = ln_1(x_out) in dtype
+ * (as f32); 1: statistics only (h == nullptr), stats_out [rows][2] = ln_1's (mean, rstd); 2: h as
+ * MX-fp8, q_out [rows][D] / qs_out [rows][D/32].  Outputs of the other modes may be NULL. */
+int clipgpu_test_vision_stem(int dtype, int x16, int mode, int64_t B, int64_t tokens, int64_t D, float eps,
+                             const float* x_in, const float* cls, const float* pos, const float* lnpre_w,
+                             const float* lnpre_b, const float* ln1_w, const float* ln1_b, float* x_out, float* h_out,
+                             float* stats_out, uint8_t* q_out, uint8_t* qs_out);
+/* Text stem (launch_text_embed_ln): x_out[b*T + t] = tok[clamp(ids[b*T + t])] + pos[t], ids [B*T] int64,
+ * tok [vocab][D], pos [npos][D] with npos >= T (a trimmed context); modes and outputs as the vision stem. */
+int clipgpu_test_text_stem(int dtype, int x16, int mode, int64_t B, int64_t T, int64_t D, int64_t vocab, int64_t npos,
+                           float eps, const int64_t* ids, const float* tok, const float* pos, const float* ln1_w,
+                           const float* ln1_b, float* x_out, float* h_out, float* stats_out, uint8_t* q_out,
+                           uint8_t* qs_out);
+/* The tails on one stream x [B*tokens][D] (f32, or f16 when x16) and ids [B*tokens] int64 (NULL = CLS
+ * pooling, else the first argmax of each sequence): pooled_out [B][D] = launch_pool_ln's LN(w, b) of the
+ * pooled row in dtype (as f32; NULL skips it), and launch_gather_pooled's raw copies (all three NULL skips
+ * it): h16_bits [B*tokens][D] 16-bit patterns, xc_out_bits [B][D] in the stream's type (4 or 2 bytes per
+ * element), hc_out_bits [B][D]. */
+int clipgpu_test_pool(int dtype, int x16, int64_t B, int64_t tokens, int64_t D, const float* x,
+                      const uint16_t* h16_bits, const int64_t* ids, const float* w, const float* b, float eps,
+                      float* pooled_out, void* xc_out_bits, uint16_t* hc_out_bits);
+/* MAP attention pool (launch_map_attention): q [D] f32 (one learned query per head, D = H * hd), kv
+ * [B*N][2*D] (k | v, rounded to dtype on upload); out [B][D] in dtype, as f32.  N <= 1024, hd % 8 == 0,
+ * hd <= 128. */
+int clipgpu_test_map_attention(int dtype, int64_t B, int64_t N, int64_t H, int64_t D, const float* q, const float* kv,
+                               float* out);
+/* out[r] = in[r] / max(||in[r]||_2, 1e-12), f32 [B][E] (launch_l2norm). */
+int clipgpu_test_l2norm(int64_t B, int64_t E, const float* in, float* out);
+/* f32 -> dtype (launch_cast_f32, the weight upload's conversion), widened back to f32. */
+int clipgpu_test_cast(int dtype, int64_t n, const float* in, float* out);
 
 /* Patch-embedding stem from normalised f32 NCHW pixels (mode 0) or u8 NHWC (mode 1), as the
  * engine runs it (patch rows, then the row GEMM with the patch epilogue):

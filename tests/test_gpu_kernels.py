@@ -3,6 +3,8 @@
 Every kernel of the hot path runs in isolation through include/clipgpu_testing.h
 hooks; inputs are pre-rounded to the kernel's 16-bit operand type so that the
 comparison isolates accumulation/epilogue error.  Tolerances are stated per test.
+(The row kernels -- LayerNorm rows and statistics, the stems, pooling, l2norm, the cast --
+and the MAP attention pool: tests/test_gpu_rowwise.py.)
 """
 import numpy as np
 import pytest
