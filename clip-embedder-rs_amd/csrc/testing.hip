@@ -94,7 +94,7 @@ void down16(DType dt, float* h, const void* d16, size_t n) {
   down(h, tmp.p, n * 4);
 }
 
-// Status of a row / MAP launcher in the hooks below: its own refusal (hipErrorInvalidValue, returned
+// Status of a row / attention launcher in the hooks below: its own refusal (hipErrorInvalidValue, returned
 // before anything is launched) is the caller's bad shape -> CLIPGPU_ERR_INVALID, so the tests can check
 // the refusals; anything else is a device error.
 void launched(hipError_t e, const char* what) {
@@ -383,11 +383,22 @@ int clipgpu_test_attention(int dtype, int64_t B, int64_t N, int64_t H, int64_t H
                            float* out) {
   return guarded([&]() {
     const DType dt = dt_of(dtype);
+    require(B > 0 && N > 0 && H > 0 && HD > 0 && B * N * 3 * H * HD < INT32_MAX && qkv && out,
+            "bad attention arguments");
     const int64_t D = H * HD;
-    DevBuf dq(B * N * 3 * D * 2), dO(B * N * D * 2);
+    // a guard after the output rows: a store for a query >= N (or of a last sequence's padded tile) lands in it
+    constexpr size_t GUARD = 4096;
+    const size_t out_bytes = (size_t)(B * N * D) * 2;
+    DevBuf dq(B * N * 3 * D * 2), dO(out_bytes + GUARD);
+    HIP_CHECK(hipMemset((char*)dO.p + out_bytes, 0xA5, GUARD));
     up16(dt, dq.p, qkv, B * N * 3 * D);
-    HIP_CHECK(launch_attention(dt, dq.p, dO.p, (int)B, (int)N, (int)H, (int)D, causal, nullptr));
+    launched(launch_attention(dt, dq.p, dO.p, (int)B, (int)N, (int)H, (int)D, causal, nullptr), "launch_attention");
     HIP_CHECK(hipDeviceSynchronize());
+    std::vector<unsigned char> guard(GUARD);
+    down(guard.data(), (char*)dO.p + out_bytes, GUARD);
+    for (size_t i = 0; i < GUARD; ++i)
+      if (guard[i] != 0xA5)
+        throw ClipErr(CLIPGPU_ERR_DEVICE, "launch_attention wrote past its output (guard byte " + std::to_string(i) + ")");
     down16(dt, out, dO.p, B * N * D);
   });
 }

@@ -19,6 +19,11 @@
  *   - an f16 stream is normalised as stored: the reference rounds the stored row to f16 first.
  *   - MAP attention: 1.01 * rel * |ref| + 1e-4 * max|v| (one output rounding plus the absolute
  *     slack the GEMM tests grant f32 accumulation; the probabilities stay in f32).
+ *   - self-attention (tests/attention_cases.py holds the derivation), per output element:
+ *       1.01 * (rel + 2 * (HD + 8) * 2^-24 * S) * (A + |ref|) + floor * V
+ *     A = sum_j p_j |v_j|, S = max_j sum_d |q_d k_jd| / sqrt(HD), V = sum_j |v_j| over the allowed keys,
+ *     floor = 2^-25 (f16: subnormal P) / 0 (bf16): P is rounded to 16 bits before P.V, the output is
+ *     rounded, and a score carries HD + 8 f32 roundings into the exp2.
  *   - l2norm: 32 * 2^-24 * |ref|;  gathers, stem sums, casts and MX bytes: bit for bit.
  * A launcher's own refusal (hipErrorInvalidValue, before anything is launched) comes back from these
  * hooks as CLIPGPU_ERR_INVALID.
@@ -52,7 +57,9 @@ int clipgpu_test_gemm_lnf(int dtype, int act, int64_t M, int64_t N, int64_t K, c
  * of large batches runs at test sizes.  Chunking is bit-invisible. */
 int clipgpu_test_gemm_chunk_rows(int64_t rows);
 
-/* qkv: [B*N][3*D] f32 (rounded to 16-bit on upload), D = H * HD (HD in {64, 72, 80}); out: [B*N][D]. */
+/* qkv: [B*N][3*D] f32 (rounded to 16-bit on upload), D = H * HD (HD in {64, 72, 80}); out: [B*N][D].
+ * launch_attention's refusals come back as CLIPGPU_ERR_INVALID; a guard after the output rows turns a
+ * store past them into CLIPGPU_ERR_DEVICE.  Bound: tests/attention_cases.py. */
 int clipgpu_test_attention(int dtype, int64_t B, int64_t N, int64_t H, int64_t HD, int causal, const float* qkv,
                            float* out);
 
