@@ -1111,6 +1111,11 @@ hipError_t launch_gemm(DType dt, int asrc, int epi, int act, const GemmParams& p
     return hipErrorInvalidValue;
   if (epi == EPI_LNF_BF) return hipErrorInvalidValue;  // internal code
   if (p.bias != nullptr && p.N % 4 != 0) return hipErrorInvalidValue;  // 16-byte bias DMA
+  // The pitch contract (kernels.hpp), for every kernel and tile, before any dispatch: operand rows are
+  // staged 16 bytes at a time (LDS-DMA / 16-byte loads), f32 and f16-stream rows are stored 4 elements at
+  // a time.  (16-bit outputs: ldo % 8 picks the pipelined tiles in launch_tile, else the general form.)
+  if (p.lda % 8 != 0 || p.ldw % 8 != 0 || p.lda < p.K || p.ldw < p.K || p.ldo < p.N) return hipErrorInvalidValue;
+  if (!epi_st16(epi) && p.ldo % 4 != 0) return hipErrorInvalidValue;
   // 32-bit staging offsets: W must fit whole; A is chunked by rows
   if ((long)p.N * p.ldw * 2 >= (1L << 31) || p.lda <= 0) return hipErrorInvalidValue;
   if (asrc != A_ROWS) return hipErrorInvalidValue;  // pixels go through launch_patch_rows first

@@ -100,6 +100,13 @@ int gemm_grid(int tile, int M, int N, int K);  // blocks of one launch (the pers
 int device_cus();  // CUs of the current device (cached)
 
 // act: Act enum from common.hpp (only used with EPI_STORE16)
+// Contract, checked before any dispatch (a violation returns hipErrorInvalidValue and launches nothing):
+//   K % 64 == 0; bias needs N % 4 == 0;
+//   lda and ldw (elements) are multiples of 8 and >= K: operand rows are staged 16 bytes at a time;
+//   ldo >= N; ldo % 4 == 0 for f32 and f16-stream outputs (EPI_RESID, EPI_STORE32, EPI_PATCH): their rows
+//   are stored 4 elements at a time;
+//   16-bit outputs (EPI_STORE16, EPI_LNF): ldo % 8 == 0 runs the pipelined tiles, any other ldo the
+//   general form (element stores where a row is not 4-aligned).
 hipError_t launch_gemm(DType dt, int asrc, int epi, int act, const GemmParams& p, hipStream_t s);
 // Kernel-boundary timing of the next GEMM launch on this thread (clipgpu_profile_*): when
 // both events are set, launch_gemm launches through hipExtLaunchKernelGGL with them, so the

@@ -2,6 +2,7 @@
 // device 0 over host f32 buffers so tests/ can check it against numpy.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <csignal>
 #include <cstdio>
@@ -332,6 +333,64 @@ int clipgpu_test_gemm(int dtype, int mode, int act, int64_t M, int64_t N, int64_
   });
 }
 
+int clipgpu_test_gemm_at(int dtype, int mode, int act, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
+                         int64_t ldo, int tile, int group, int prio, const float* A, const float* W, const float* bias,
+                         float* resid_out) {
+  return guarded([&]() {
+    const DType dt = dt_of(dtype);
+    require(M > 0 && N > 0 && K > 0 && lda > 0 && ldw > 0 && ldo > 0 && mode >= 0 && mode <= 3 && A && W && resid_out,
+            "bad GEMM arguments");
+    require(M * std::max(lda, K) < INT32_MAX && N * std::max(ldw, K) < INT32_MAX && M * std::max(ldo, N) < INT32_MAX,
+            "GEMM too large for the hook");
+    // device buffers cover [rows][max(pitch, the kernel's extent)]: a pitch the launcher must refuse is
+    // never a buffer overrun here, whatever the launcher does
+    const int64_t nA = M * lda, nW = N * ldw, nO = M * ldo;
+    DevBuf dA(M * std::max(lda, K) * 2), dW(N * std::max(ldw, K) * 2), dB((N + 4) * 4),
+        dO(M * std::max(ldo, N + 8) * 4);
+    up16(dt, dA.p, A, nA);
+    up16(dt, dW.p, W, nW);
+    if (bias) up(dB.p, bias, N * 4);
+    GemmParams g{};
+    g.tile = tile; g.group = group; g.prio = prio;
+    g.A = dA.p; g.lda = lda; g.W = dW.p; g.ldw = ldw; g.bias = bias ? dB.as<float>() : nullptr;
+    g.out = dO.p; g.ldo = ldo; g.M = (int)M; g.N = (int)N; g.K = (int)K;
+    g.x16 = mode == 3;
+    const int epi = mode == 0 ? EPI_STORE16 : mode == 2 ? EPI_STORE32 : EPI_RESID;
+    // the whole [M][ldo] buffer travels both ways: the residual (or the prefill) and the pad columns
+    if (mode == 0) up16(dt, dO.p, resid_out, nO);
+    else up_stream(mode == 3, dO.p, resid_out, nO);
+    launched(launch_gemm(dt, A_ROWS, epi, mode == 0 ? act : 0, g, nullptr), "launch_gemm");
+    HIP_CHECK(hipDeviceSynchronize());
+    if (mode == 0) down16(dt, resid_out, dO.p, nO);
+    else down_stream(mode == 3, resid_out, dO.p, nO);
+  });
+}
+
+int clipgpu_test_patch_gemm(int dtype, int x16, int cls, int64_t B, int64_t G, int64_t Kp, int64_t D, int tile,
+                            const float* rows, const float* W, const float* bias, const float* pos, float* x_inout) {
+  return guarded([&]() {
+    const DType dt = dt_of(dtype);
+    require(B > 0 && G > 0 && Kp > 0 && D > 0 && (cls == 0 || cls == 1) && rows && W && pos && x_inout,
+            "bad patch GEMM arguments");
+    const int64_t M = B * G * G, tokens = G * G + cls;
+    require(M * Kp < INT32_MAX && D * Kp < INT32_MAX && B * tokens * D < INT32_MAX,
+            "patch GEMM too large for the hook");
+    DevBuf dA(M * Kp * 2), dW(D * Kp * 2), dB((D + 4) * 4), dpos(tokens * D * 4), dx(B * tokens * D * 4);
+    up16(dt, dA.p, rows, M * Kp);
+    up16(dt, dW.p, W, D * Kp);
+    if (bias) up(dB.p, bias, D * 4);
+    up(dpos.p, pos, tokens * D * 4);
+    up_stream(x16, dx.p, x_inout, B * tokens * D);
+    GemmParams g{};
+    g.A = dA.p; g.lda = Kp; g.W = dW.p; g.ldw = Kp; g.bias = bias ? dB.as<float>() : nullptr;
+    g.out = dx.p; g.ldo = D; g.M = (int)M; g.N = (int)D; g.K = (int)Kp;
+    g.cls = cls; g.G = (int)G; g.pos = dpos.as<float>(); g.x16 = x16 ? 1 : 0; g.tile = tile;
+    launched(launch_gemm(dt, A_ROWS, EPI_PATCH, 0, g, nullptr), "launch_gemm (patch)");
+    HIP_CHECK(hipDeviceSynchronize());
+    down_stream(x16, x_inout, dx.p, B * tokens * D);
+  });
+}
+
 int clipgpu_test_gemm_chunk_rows(int64_t rows) {
   return guarded([&]() {
     if (rows < 0) throw ClipErr(CLIPGPU_ERR_INVALID, "rows < 0");
@@ -355,28 +414,42 @@ int clipgpu_test_topk_key(float score, uint32_t index, uint64_t* key) {
   });
 }
 
+}  // extern "C"
+
+namespace {
+void run_gemm_lnf(int dtype, int act, int64_t M, int64_t N, int64_t K, const float* x, const float* wf, const float* cs,
+                  const float* bias, float eps, int tile, int group, int prio, float* out) {
+  const DType dt = dt_of(dtype);
+  if (M <= 0 || N <= 0 || K <= 0 || K % 64 || N % 4) throw ClipErr(CLIPGPU_ERR_INVALID, "bad GEMM shape");
+  if (tile != 0 && tile != TILE_SKINNY && tile != TILE_GENERAL && !gemm_tile_built(tile))
+    throw ClipErr(CLIPGPU_ERR_INVALID, "bad tile");
+  DevBuf dA(M * K * 2), dW(N * K * 2), dB(N * 4), dC(N * 4), dO(M * N * 2), dS((M + 256) * 8);
+  up16(DT_F16, dA.p, x, M * K);
+  up16(DT_F16, dW.p, wf, N * K);
+  up(dB.p, bias, N * 4);
+  up(dC.p, cs, N * 4);
+  HIP_CHECK(launch_ln_stats(dA.p, 1, eps, dS.as<float>(), (int)M, (int)K, nullptr));  // the rows' (mean, rstd)
+  GemmParams g{};
+  g.tile = tile; g.group = group; g.prio = prio;
+  g.A = dA.p; g.lda = K; g.W = dW.p; g.ldw = K; g.bias = dB.as<float>(); g.cs = dC.as<float>();
+  g.rowstats = dS.as<float>();
+  g.out = dO.p; g.ldo = N; g.M = (int)M; g.N = (int)N; g.K = (int)K;
+  launched(launch_gemm(dt, A_ROWS, EPI_LNF, act, g, nullptr), "launch_gemm (EPI_LNF)");
+  HIP_CHECK(hipDeviceSynchronize());
+  down16(dt, out, dO.p, M * N);
+}
+}  // namespace
+
+extern "C" {
+
 int clipgpu_test_gemm_lnf(int dtype, int act, int64_t M, int64_t N, int64_t K, const float* x, const float* wf,
                           const float* cs, const float* bias, float eps, int tile, float* out) {
-  return guarded([&]() {
-    const DType dt = dt_of(dtype);
-    if (M <= 0 || N <= 0 || K <= 0 || K % 64 || N % 4) throw ClipErr(CLIPGPU_ERR_INVALID, "bad GEMM shape");
-    if (tile != 0 && tile != TILE_SKINNY && tile != TILE_GENERAL && !gemm_tile_built(tile))
-      throw ClipErr(CLIPGPU_ERR_INVALID, "bad tile");
-    DevBuf dA(M * K * 2), dW(N * K * 2), dB(N * 4), dC(N * 4), dO(M * N * 2), dS((M + 256) * 8);
-    up16(DT_F16, dA.p, x, M * K);
-    up16(DT_F16, dW.p, wf, N * K);
-    up(dB.p, bias, N * 4);
-    up(dC.p, cs, N * 4);
-    HIP_CHECK(launch_ln_stats(dA.p, 1, eps, dS.as<float>(), (int)M, (int)K, nullptr));  // the rows' (mean, rstd)
-    GemmParams g{};
-    g.tile = tile;
-    g.A = dA.p; g.lda = K; g.W = dW.p; g.ldw = K; g.bias = dB.as<float>(); g.cs = dC.as<float>();
-    g.rowstats = dS.as<float>();
-    g.out = dO.p; g.ldo = N; g.M = (int)M; g.N = (int)N; g.K = (int)K;
-    HIP_CHECK(launch_gemm(dt, A_ROWS, EPI_LNF, act, g, nullptr));
-    HIP_CHECK(hipDeviceSynchronize());
-    down16(dt, out, dO.p, M * N);
-  });
+  return guarded([&]() { run_gemm_lnf(dtype, act, M, N, K, x, wf, cs, bias, eps, tile, 0, 0, out); });
+}
+
+int clipgpu_test_gemm_lnf_at(int dtype, int act, int64_t M, int64_t N, int64_t K, const float* x, const float* wf,
+                             const float* cs, const float* bias, float eps, int tile, int group, int prio, float* out) {
+  return guarded([&]() { run_gemm_lnf(dtype, act, M, N, K, x, wf, cs, bias, eps, tile, group, prio, out); });
 }
 
 int clipgpu_test_attention(int dtype, int64_t B, int64_t N, int64_t H, int64_t HD, int causal, const float* qkv,
@@ -618,39 +691,67 @@ int clipgpu_test_layernorm_mx(int64_t rows, int64_t D, float eps, const float* x
   });
 }
 
+}  // extern "C"
+
+namespace {
+// mode 0 store16 (act), 1 residual f32, 2 store32, 3 MX-fp8 output (act), 4 residual on an f16 stream.  A is
+// [M][lda] / W [N][ldw] bytes, their scales [M][K/32] / [N][K/32]; the launcher's refusals -> CLIPGPU_ERR_INVALID.
+void run_gemm_mx(int dtype, int mode, int act, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw, int tile,
+                 const uint8_t* Aq, const uint8_t* As, const uint8_t* Wq, const uint8_t* Ws, const float* bias,
+                 const float* resid, float* out, uint8_t* outq, uint8_t* outs) {
+  const DType dt = dt_of(dtype);
+  if (M <= 0 || N <= 0 || K <= 0 || K % 128 || N % 32 || mode < 0 || mode > 4 || lda <= 0 || ldw <= 0)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "bad MX GEMM shape (K % 128 == 0, N % 32 == 0)");
+  require(Aq && As && Wq && Ws && (mode == 3 ? (outq && outs) : out != nullptr), "missing MX GEMM buffer");
+  DevBuf dA(M * std::max(lda, K)), dAs(M * K / 32), dW(N * std::max(ldw, K)), dWs(N * K / 32), dB(N * 4),
+      dO(M * N * 4), dOs(M * N / 32);
+  up(dA.p, Aq, M * lda);
+  up(dAs.p, As, M * K / 32);
+  up(dW.p, Wq, N * ldw);
+  up(dWs.p, Ws, N * K / 32);
+  if (bias) up(dB.p, bias, N * 4);
+  MxGemmParams g{};
+  g.A = dA.as<uint8_t>(); g.lda = lda; g.As = dAs.as<uint8_t>(); g.ldas = K / 32;
+  g.W = dW.as<uint8_t>(); g.ldw = ldw; g.Ws = dWs.as<uint8_t>(); g.ldws = K / 32;
+  g.bias = bias ? dB.as<float>() : nullptr;
+  g.out = dO.p; g.M = (int)M; g.N = (int)N; g.K = (int)K; g.tile = tile;
+  static const int epis[5] = {EPI_STORE16, EPI_RESID, EPI_STORE32, EPI_STOREQ, EPI_RESID};
+  const int epi = epis[mode];
+  g.x16 = mode == 4;
+  g.ldo = N;
+  if (epi == EPI_STOREQ) {
+    g.outs = dOs.as<uint8_t>();
+    g.ldos = N / 32;
+  }
+  if (epi == EPI_RESID && resid) up_stream(g.x16, dO.p, resid, M * N);
+  launched(launch_gemm_mx(dt, epi, act, g, nullptr), "launch_gemm_mx");
+  HIP_CHECK(hipDeviceSynchronize());
+  if (epi == EPI_STORE16) down16(dt, out, dO.p, M * N);
+  else if (epi == EPI_STOREQ) {
+    down(outq, dO.p, M * N);
+    down(outs, dOs.p, M * N / 32);
+  } else down_stream(g.x16, out, dO.p, M * N);
+}
+}  // namespace
+
+extern "C" {
+
 int clipgpu_test_gemm_mx(int dtype, int mode, int act, int64_t M, int64_t N, int64_t K, const uint8_t* Aq,
                          const uint8_t* As, const uint8_t* Wq, const uint8_t* Ws, const float* bias, const float* resid,
                          float* out, uint8_t* outq, uint8_t* outs) {
   return guarded([&]() {
-    const DType dt = dt_of(dtype);
-    if (M <= 0 || N <= 0 || K <= 0 || K % 128 || N % 32 || mode < 0 || mode > 3)
-      throw ClipErr(CLIPGPU_ERR_INVALID, "bad MX GEMM shape (K % 128 == 0, N % 32 == 0)");
-    DevBuf dA(M * K), dAs(M * K / 32), dW(N * K), dWs(N * K / 32), dB(N * 4), dO(M * N * 4), dOs(M * N / 32);
-    up(dA.p, Aq, M * K);
-    up(dAs.p, As, M * K / 32);
-    up(dW.p, Wq, N * K);
-    up(dWs.p, Ws, N * K / 32);
-    if (bias) up(dB.p, bias, N * 4);
-    MxGemmParams g{};
-    g.A = dA.as<uint8_t>(); g.lda = K; g.As = dAs.as<uint8_t>(); g.ldas = K / 32;
-    g.W = dW.as<uint8_t>(); g.ldw = K; g.Ws = dWs.as<uint8_t>(); g.ldws = K / 32;
-    g.bias = bias ? dB.as<float>() : nullptr;
-    g.out = dO.p; g.M = (int)M; g.N = (int)N; g.K = (int)K; g.tile = tile_override();
-    static const int epis[4] = {EPI_STORE16, EPI_RESID, EPI_STORE32, EPI_STOREQ};
-    const int epi = epis[mode];
-    g.ldo = N;
-    if (epi == EPI_STOREQ) {
-      g.outs = dOs.as<uint8_t>();
-      g.ldos = N / 32;
-    }
-    if (epi == EPI_RESID && resid) up(dO.p, resid, M * N * 4);
-    HIP_CHECK(launch_gemm_mx(dt, epi, (epi == EPI_STORE16 || epi == EPI_STOREQ) ? act : 0, g, nullptr));
-    HIP_CHECK(hipDeviceSynchronize());
-    if (epi == EPI_STORE16) down16(dt, out, dO.p, M * N);
-    else if (epi == EPI_STOREQ) {
-      down(outq, dO.p, M * N);
-      down(outs, dOs.p, M * N / 32);
-    } else down(out, dO.p, M * N * 4);
+    // (the activation goes to the launcher as given: it refuses one on the f32 / residual epilogues)
+    const char* e = getenv("CLIPGPU_TEST_TILE");
+    run_gemm_mx(dtype, mode, act, M, N, K, K, K, e ? atoi(e) : 0, Aq, As, Wq, Ws, bias, resid, out, outq, outs);
+  });
+}
+
+int clipgpu_test_gemm_mx_at(int dtype, int mode, int act, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
+                            int tile, const uint8_t* Aq, const uint8_t* As, const uint8_t* Wq, const uint8_t* Ws,
+                            const float* bias, const float* resid, float* out) {
+  return guarded([&]() {
+    require(mode != 3, "clipgpu_test_gemm_mx_at: modes 0, 1, 2, 4");
+    run_gemm_mx(dtype, mode, act, M, N, K, lda, ldw, tile, Aq, As, Wq, Ws, bias, resid, out, nullptr, nullptr);
   });
 }
 

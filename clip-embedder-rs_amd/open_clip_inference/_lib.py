@@ -76,6 +76,11 @@ _PROTOS = [
     ("clipgpu_synth_tensor", c_int, [c_uint64, c_char_p, c_double, c_double, c_void_p, c_int64]),
     # include/clipgpu_testing.h
     ("clipgpu_test_gemm", c_int, [c_int, c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("clipgpu_test_gemm_at", c_int, [c_int, c_int, c_int] + [c_int64] * 6 + [c_int, c_int, c_int] + [c_void_p] * 4),
+    ("clipgpu_test_patch_gemm", c_int, [c_int, c_int, c_int] + [c_int64] * 4 + [c_int] + [c_void_p] * 5),
+    ("clipgpu_test_gemm_lnf_at", c_int, [c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_float, c_int, c_int, c_int, c_void_p]),
+    ("clipgpu_test_gemm_mx_at", c_int, [c_int, c_int, c_int] + [c_int64] * 5 + [c_int] + [c_void_p] * 7),
     ("clipgpu_test_gemm_chunk_rows", c_int, [c_int64]),
     ("clipgpu_test_topk_span_cols", c_int, [c_int64]),
     ("clipgpu_test_topk_key", c_int, [c_float, ctypes.c_uint32, POINTER(c_uint64)]),

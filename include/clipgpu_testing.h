@@ -52,6 +52,30 @@ int clipgpu_test_gemm(int dtype, int mode, int act, int64_t M, int64_t N, int64_
 int clipgpu_test_gemm_lnf(int dtype, int act, int64_t M, int64_t N, int64_t K, const float* x, const float* wf,
                           const float* cs, const float* bias, float eps, int tile, float* out);
 
+/* clipgpu_test_gemm_lnf with the tile order (GemmParams.group) and wave priority (GemmParams.prio) the
+ * engine's sites launch with: speed only, so bit-equal to clipgpu_test_gemm_lnf. */
+int clipgpu_test_gemm_lnf_at(int dtype, int act, int64_t M, int64_t N, int64_t K, const float* x, const float* wf,
+                             const float* cs, const float* bias, float eps, int tile, int group, int prio, float* out);
+/* launch_gemm at explicit launch parameters (tests/test_gpu_gemm.py).  Modes as clipgpu_test_gemm; tile is
+ * explicit (CLIPGPU_TEST_TILE is not read), group / prio as GemmParams.  A [M][lda], W [N][ldw] (f32 on the
+ * host, rounded to dtype on upload, the pad columns >= K uploaded as given); resid_out [M][ldo] is uploaded
+ * whole before the launch (the residual of modes 1 / 3; modes 0 / 3 round it to the output type: pass exact
+ * values) and read back whole after it, so the pad columns >= N show whether anything wrote them.  The
+ * launcher's refusals (kernels.hpp: the pitch contract, an unbuilt tile, ...) come back as
+ * CLIPGPU_ERR_INVALID with resid_out untouched.
+ * The tests of these hooks use small-integer operands: every product and partial sum is then an integer
+ * below 2^24, the f32 accumulator is exact in any order, and the epilogue -- (acc + bias) + x in f32, one
+ * rounding to the output type -- is reproduced by numpy bit for bit: they compare with ==. */
+int clipgpu_test_gemm_at(int dtype, int mode, int act, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
+                         int64_t ldo, int tile, int group, int prio, const float* A, const float* W, const float* bias,
+                         float* resid_out);
+/* The patch GEMM alone (EPI_PATCH) on given patch rows [B*G*G][Kp] and W [D][Kp] (rounded to dtype on
+ * upload), bias [D] or NULL, pos [G*G+cls][D]: x_inout [B*(G*G+cls)][D] is uploaded before the launch (as
+ * f16 when x16: pass exact values) and read back after it: patch p of image b lands in row
+ * b*(G*G+cls) + cls + p as rows.W^T + bias + pos[cls + p]; the class rows (cls = 1) stay as uploaded. */
+int clipgpu_test_patch_gemm(int dtype, int x16, int cls, int64_t B, int64_t G, int64_t Kp, int64_t D, int tile,
+                            const float* rows, const float* W, const float* bias, const float* pos, float* x_inout);
+
 /* Cap the rows of one GEMM launch of launch_gemm's row-chunked path (0 = off: only the 2^31-byte operand
  * limit chunks), process-wide, for every GEMM launched (or graph captured) afterwards: the chunked path
  * of large batches runs at test sizes.  Chunking is bit-invisible. */
@@ -177,11 +201,19 @@ int clipgpu_test_layernorm_mx(int64_t rows, int64_t D, float eps, const float* x
 
 /* MX-fp8 GEMM on given MX operands A (Aq [M][K], As [M][K/32]) and W (Wq [N][K], Ws [N][K/32]):
  * mode 0: act(A.W^T + bias) as 16-bit (returned as f32 in out); 1: out = resid + A.W^T + bias (f32);
- * 2: f32 A.W^T + bias; 3: MX-fp8 of act(A.W^T + bias) into outq [M][N] / outs [M][N/32].
- * K % 128 == 0, N % 32 == 0; CLIPGPU_TEST_TILE picks the MxTile (0 auto, 2 256x128, 3 128x128). */
+ * 2: f32 A.W^T + bias; 3: MX-fp8 of act(A.W^T + bias) into outq [M][N] / outs [M][N/32]; 4: mode 1 on an
+ * f16 residual stream (MxGemmParams.x16: resid rounded to f16 on upload, the f16 result widened exactly).
+ * K % 128 == 0, N % 32 == 0; CLIPGPU_TEST_TILE picks the MxTile (0 auto, 2 256x128, 3 128x128).  act goes
+ * to the launcher as given; its refusals (an activation on modes 1 / 2 / 4, an unbuilt tile) come back as
+ * CLIPGPU_ERR_INVALID. */
 int clipgpu_test_gemm_mx(int dtype, int mode, int act, int64_t M, int64_t N, int64_t K, const uint8_t* Aq,
                          const uint8_t* As, const uint8_t* Wq, const uint8_t* Ws, const float* bias,
                          const float* resid, float* out, uint8_t* outq, uint8_t* outs);
+/* The same (modes 0, 1, 2, 4) with explicit row pitches of the code bytes, Aq [M][lda] / Wq [N][ldw] (the
+ * scales stay [rows][K/32]), and an explicit MxTile. */
+int clipgpu_test_gemm_mx_at(int dtype, int mode, int act, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
+                            int tile, const uint8_t* Aq, const uint8_t* As, const uint8_t* Wq, const uint8_t* Ws,
+                            const float* bias, const float* resid, float* out);
 
 /* Device-resident MX GEMM timing (random operands quantized on the device), epi as mode above. */
 int clipgpu_test_gemm_mx_bench(int epi, int act, int64_t M, int64_t N, int64_t K, int tile, int iters,
