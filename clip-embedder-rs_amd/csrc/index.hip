@@ -34,12 +34,16 @@ struct clipgpu_index {
   std::mutex mu;
   int device = 0;
   int64_t E = 0, capacity = 0, size = 0;
-  float* gallery = nullptr;  // [capacity][E]
+  int dtype = CLIPGPU_INDEX_F32;  // the gallery's element type
+  int64_t esz = 4;                // its bytes
+  char* gallery = nullptr;        // [capacity][E] of esz bytes
   char* work = nullptr;      // ws | staged queries | staged indices | staged scores
   int ws_blocks = 0;         // phase-1 blocks the workspace holds: min(kMaxBlocks, 4 * 64-row tiles of capacity)
   float* st_q = nullptr;
   int64_t* st_idx = nullptr;
   float* st_score = nullptr;
+  float* scratch = nullptr;      // 16-bit index: f32 rows on their way in (add) or out (get_rows); lazy
+  size_t scratch_bytes = 0;
   hipStream_t stream = nullptr;  // the host-buffer forms' stream
   hipEvent_t done = nullptr;     // recorded after every device-side operation
 };
@@ -69,11 +73,27 @@ void search_on(clipgpu_index* ix, const float* d_q, int64_t nq, int64_t k, float
   order_after_last(ix, s);
   for (int64_t q0 = 0; q0 < nq; q0 += kQueryChunk) {
     const int rows = (int)std::min(kQueryChunk, nq - q0);
-    const TopkPlan p = topk_plan(ix->size, (rows + 63) / 64, ix->ws_blocks);
-    HIP_CHECK(launch_topk(d_q + q0 * ix->E, rows, ix->gallery, (int)ix->size, (int)ix->E, scale, bias, (int)k, p,
-                         ix->work, d_idx + q0 * k, d_score + q0 * k, s));
+    const TopkPlan p = topk_plan(ix->size, rows, ix->ws_blocks);  // the route too: few rows, few-query kernel
+    HIP_CHECK(launch_topk(d_q + q0 * ix->E, rows, ix->gallery, ix->dtype, (int)ix->size, (int)ix->E, scale, bias,
+                         (int)k, p, ix->work, d_idx + q0 * k, d_score + q0 * k, s));
   }
   mark_last(ix, s);
+}
+
+// Device scratch for the f32 side of a 16-bit index's host-row add / export, in pieces of at most 64 MiB
+// (one row if a row is larger).  The handle keeps it: allocated at the first use, grown if a later call
+// needs more, freed with the handle.  Callers hold the mutex and have waited for `done`.
+int64_t piece_rows(const clipgpu_index* ix) { return std::max<int64_t>(1, (64LL << 20) / (ix->E * 4)); }
+float* scratch_for(clipgpu_index* ix, int64_t rows) {
+  const size_t need = (size_t)rows * ix->E * 4;
+  if (need > ix->scratch_bytes) {
+    if (ix->scratch) HIP_CHECK(hipFree(ix->scratch));
+    ix->scratch = nullptr;
+    ix->scratch_bytes = 0;
+    HIP_CHECK(hipMalloc((void**)&ix->scratch, need));
+    ix->scratch_bytes = need;
+  }
+  return ix->scratch;
 }
 
 }  // namespace
@@ -81,9 +101,15 @@ void search_on(clipgpu_index* ix, const float* d_q, int64_t nq, int64_t k, float
 extern "C" {
 
 int clipgpu_index_create(int device, int64_t E, int64_t capacity, clipgpu_index** out) {
+  return clipgpu_index_create_ex(device, E, capacity, CLIPGPU_INDEX_F32, out);
+}
+
+int clipgpu_index_create_ex(int device, int64_t E, int64_t capacity, int dtype, clipgpu_index** out) {
   return guarded([&]() {
     if (!out) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL out");
     *out = nullptr;
+    if (dtype != CLIPGPU_INDEX_F32 && dtype != CLIPGPU_INDEX_F16 && dtype != CLIPGPU_INDEX_BF16)
+      throw ClipErr(CLIPGPU_ERR_INVALID, "unknown index dtype");
     if (E <= 0 || E % 16) throw ClipErr(CLIPGPU_ERR_INVALID, "Shape error: embedding dim must be a multiple of 16");
     if (capacity <= 0) throw ClipErr(CLIPGPU_ERR_INVALID, "capacity must be positive");
     if (capacity >= (1LL << 31) || E > (1 << 20) || capacity > (1LL << 46) / (E * 4))
@@ -94,11 +120,13 @@ int clipgpu_index_create(int device, int64_t E, int64_t capacity, clipgpu_index*
     ix->device = device;
     ix->E = E;
     ix->capacity = capacity;
+    ix->dtype = dtype;
+    ix->esz = topk_gal_bytes(dtype);
     ix->ws_blocks = (int)std::min<int64_t>(kMaxBlocks, 4 * ((capacity + 63) / 64));
     const size_t ws = align256((size_t)ix->ws_blocks * 64 * kTopkMax * 8);
     const size_t sq = align256((size_t)kQueryChunk * E * 4), si = align256((size_t)kQueryChunk * kTopkMax * 8);
     const size_t ss = align256((size_t)kQueryChunk * kTopkMax * 4);
-    hipError_t err = hipMalloc((void**)&ix->gallery, (size_t)capacity * E * 4);
+    hipError_t err = hipMalloc((void**)&ix->gallery, (size_t)capacity * E * ix->esz);
     if (err == hipSuccess) err = hipMalloc((void**)&ix->work, ws + sq + si + ss);
     if (err == hipSuccess) err = hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking);
     if (err == hipSuccess) err = hipEventCreateWithFlags(&ix->done, hipEventDisableTiming);
@@ -121,6 +149,7 @@ void clipgpu_index_destroy(clipgpu_index* ix) {
     (void)hipEventDestroy(ix->done);
   }
   if (ix->stream) (void)hipStreamDestroy(ix->stream);
+  if (ix->scratch) (void)hipFree(ix->scratch);
   if (ix->work) (void)hipFree(ix->work);
   if (ix->gallery) (void)hipFree(ix->gallery);
   delete ix;
@@ -148,7 +177,11 @@ int clipgpu_index_add_device(clipgpu_index* ix, const float* d_rows, int64_t n, 
     HIP_CHECK(hipSetDevice(ix->device));
     hipStream_t s = (hipStream_t)stream;
     order_after_last(ix, s);
-    HIP_CHECK(hipMemcpyAsync(ix->gallery + ix->size * ix->E, d_rows, (size_t)n * ix->E * 4, hipMemcpyDeviceToDevice, s));
+    char* dst = ix->gallery + ix->size * ix->E * ix->esz;
+    if (ix->dtype == CLIPGPU_INDEX_F32)
+      HIP_CHECK(hipMemcpyAsync(dst, d_rows, (size_t)n * ix->E * 4, hipMemcpyDeviceToDevice, s));
+    else
+      HIP_CHECK(launch_gal_round(ix->dtype, d_rows, dst, n * ix->E, s));
     mark_last(ix, s);
     ix->size += n;
   });
@@ -161,8 +194,46 @@ int clipgpu_index_add(clipgpu_index* ix, const float* rows, int64_t n) {
     if (n > ix->capacity - ix->size) throw ClipErr(CLIPGPU_ERR_INVALID, "index full");
     HIP_CHECK(hipSetDevice(ix->device));
     HIP_CHECK(hipEventSynchronize(ix->done));
-    HIP_CHECK(copy_h2d(ix->gallery + ix->size * ix->E, rows, (size_t)n * ix->E * 4));
+    char* dst = ix->gallery + ix->size * ix->E * ix->esz;
+    if (ix->dtype == CLIPGPU_INDEX_F32) {
+      HIP_CHECK(copy_h2d(dst, rows, (size_t)n * ix->E * 4));
+    } else {  // the f32 rows go to device scratch and are rounded there
+      const int64_t piece = std::min(n, piece_rows(ix));
+      float* f32 = scratch_for(ix, piece);
+      for (int64_t r0 = 0; r0 < n; r0 += piece) {
+        const int64_t m = std::min(piece, n - r0);
+        HIP_CHECK(copy_h2d(f32, rows + r0 * ix->E, (size_t)m * ix->E * 4));
+        HIP_CHECK(launch_gal_round(ix->dtype, f32, dst + r0 * ix->E * ix->esz, m * ix->E, ix->stream));
+        HIP_CHECK(hipStreamSynchronize(ix->stream));
+      }
+    }
     ix->size += n;
+  });
+}
+
+int clipgpu_index_dtype(const clipgpu_index* ix) { return ix ? ix->dtype : -1; }
+
+int clipgpu_index_get_rows(clipgpu_index* ix, int64_t first, int64_t n, float* out_rows) {
+  return guarded([&]() {
+    if (!ix || !out_rows) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (first < 0 || n <= 0 || n > ix->size || first > ix->size - n)
+      throw ClipErr(CLIPGPU_ERR_INVALID, "rows out of range (first >= 0, n >= 1, first + n <= size)");
+    HIP_CHECK(hipSetDevice(ix->device));
+    HIP_CHECK(hipEventSynchronize(ix->done));
+    const char* src = ix->gallery + first * ix->E * ix->esz;
+    if (ix->dtype == CLIPGPU_INDEX_F32) {
+      HIP_CHECK(copy_d2h(out_rows, src, (size_t)n * ix->E * 4));
+      return;
+    }
+    const int64_t piece = std::min(n, piece_rows(ix));
+    float* f32 = scratch_for(ix, piece);
+    for (int64_t r0 = 0; r0 < n; r0 += piece) {
+      const int64_t m = std::min(piece, n - r0);
+      HIP_CHECK(launch_gal_widen(ix->dtype, src + r0 * ix->E * ix->esz, f32, m * ix->E, ix->stream));
+      HIP_CHECK(hipStreamSynchronize(ix->stream));
+      HIP_CHECK(copy_d2h(out_rows + r0 * ix->E, f32, (size_t)m * ix->E * 4));
+    }
   });
 }
 

@@ -191,13 +191,30 @@ hipError_t launch_similarity(const float* img, int ni, const float* txt, int nt,
 // -inf there).  The gallery is cut into n_spans spans of span_cols columns (a multiple of 64); ws
 // holds ceil(nq / 64) * 64 * n_spans * k entries of 8 bytes.  1 <= k <= kTopkMax, E % 16 == 0.
 constexpr int kTopkMax = 128;
-struct TopkPlan { int span_cols, n_spans; };
-// The span cut for N gallery rows and q_tiles 64-query tiles with at most max_blocks phase-1 blocks
-// (the workspace bound): as many spans as tiles and max_blocks allow, or g_topk_span_cols columns per
-// span when that test hook is set (clipgpu_test_topk_span_cols; 0 = off).
+// The gallery's element type (the values of clipgpu_index_dtype).  A 16-bit element is widened in
+// registers, exactly, so a 16-bit gallery gives the bits an f32 gallery of the widened rows gives.
+enum TopkGal { TOPK_GAL_F32 = 0, TOPK_GAL_F16 = 1, TOPK_GAL_BF16 = 2 };
+int topk_gal_bytes(int dtype);
+// f32 -> f16 / bf16 rows, round to nearest even (f16: subnormals kept, |x| >= 65520 -> inf; NaN stays
+// NaN, -0.0 stays -0.0), and back (exact).  n elements, n % 4 == 0, both sides 16-byte / 8-byte aligned.
+hipError_t launch_gal_round(int dtype, const float* in, void* out, long n, hipStream_t s);
+hipError_t launch_gal_widen(int dtype, const void* in, float* out, long n, hipStream_t s);
+// Phase 1 has two kernels with the same results: the wide one (64-query tiles) and the few-query one (one
+// 16-row tile, one wave per block).  A launch of at most kNarrowRows query rows takes the few-query one;
+// g_topk_route (clipgpu_test_topk_route) overrides: 1 = always wide, 2 = few-query for every nq <= 16.
+// kNarrowRows is measured (embedding index): the largest nq at which the few-query route's
+// median is below the wide route's.
+constexpr int kNarrowRows = 16;
+constexpr int kNarrowSpans = 2048;  // most spans of a few-query launch (8 one-wave blocks per CU)
+struct TopkPlan { int span_cols, n_spans; bool narrow; };
+// The route and the span cut for N gallery rows and nq query rows, with a workspace sized for max_blocks
+// wide phase-1 blocks: as many spans as 64-column tiles and the workspace allow (few-query route: at
+// most kNarrowSpans), or g_topk_span_cols columns per span when that test hook is set
+// (clipgpu_test_topk_span_cols; 0 = off).
 extern std::atomic<long> g_topk_span_cols;
-TopkPlan topk_plan(long N, int q_tiles, int max_blocks);
-hipError_t launch_topk(const float* q, int nq, const float* g, int N, int E, float scale, float bias, int k,
+extern std::atomic<int> g_topk_route;
+TopkPlan topk_plan(long N, int nq, int max_blocks);
+hipError_t launch_topk(const float* q, int nq, const void* g, int dtype, int N, int E, float scale, float bias, int k,
                        const TopkPlan& p, void* ws, int64_t* out_idx, float* out_score, hipStream_t s);
 
 // out[r] = in[r] / max(||in[r]||_2, 1e-12)

@@ -19,6 +19,10 @@
 // Phase 2 (topk_merge_kernel): one wave per query row runs the same threshold / ballot / compact
 // selection over the row's n_spans * k workspace entries and writes int64 indices and f32 scores,
 // best first; slots beyond min(k, N) are (-1, -inf).
+//
+// The gallery is stored as f32, f16 or bf16 (TopkGal); a 16-bit element is widened in registers, which
+// is exact, so the dot products run on the same f32 chain over widen(row).  A chunk of at most 16 query
+// rows may take the few-query phase 1 instead (topk_narrow_kernel, below): same bits, same order.
 #include <algorithm>
 #include <atomic>
 #include <cstdint>
@@ -30,6 +34,7 @@
 namespace clipgpu {
 
 std::atomic<long> g_topk_span_cols{0};
+std::atomic<int> g_topk_route{0};
 
 namespace {
 
@@ -37,6 +42,9 @@ constexpr int TB = 64, TK = 64;
 constexpr int KQ = 20, LDT = 88;  // staged row: 4 k slots of 16 steps + 4, + 8: conflict-free 16-byte reads
 constexpr int CAND1 = 32;  // phase 1 candidate slots per row (one ballot adds at most 16 to a row)
 constexpr int CAND2 = 64;  // phase 2 (one ballot adds at most 64)
+#ifndef CLIPGPU_TOPK_MERGE_STEPS
+#define CLIPGPU_TOPK_MERGE_STEPS 4  // 64-entry steps the merge loads at once
+#endif
 
 // A selection entry: x = the score's own f32 bits, y = gallery index.  Compared by topk_key.
 __device__ __forceinline__ uint64_t ent_key(uint2 e) { return topk_key(e.x, e.y); }
@@ -46,6 +54,30 @@ __device__ __forceinline__ uint2 ent_empty() { return make_uint2(kTopkEmptyScore
 __device__ __forceinline__ void wave_lds_order() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
+}
+
+// Four consecutive 16-bit gallery elements as f32: one 8-byte load, widened (exactly).
+__device__ __forceinline__ float4 gal4(const _Float16* p) {
+  const f16x4 h = *(const f16x4*)p;
+  return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+}
+__device__ __forceinline__ float4 gal4(const __bf16* p) {
+  const uint2 u = *(const uint2*)p;
+  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                     __uint_as_float(u.y & 0xffff0000u));
+}
+
+// The same elements as loaded (held in registers while the loads are in flight) and widened when staged.
+template <typename GT> struct GalRaw { typedef uint2 type; };
+template <> struct GalRaw<float> { typedef float4 type; };
+__device__ __forceinline__ float4 gal_raw(const float* p) { return *(const float4*)p; }
+__device__ __forceinline__ uint2 gal_raw(const _Float16* p) { return *(const uint2*)p; }
+__device__ __forceinline__ uint2 gal_raw(const __bf16* p) { return *(const uint2*)p; }
+template <typename GT> __device__ __forceinline__ float4 gal_widen(float4 v) { return v; }
+template <typename GT> __device__ __forceinline__ float4 gal_widen(uint2 u) {
+  union { uint2 u; GT h[4]; } x;
+  x.u = u;
+  return gal4(x.h);
 }
 
 // Wave-cooperative (all 64 lanes, uniform arguments).  ent[0 .. k) is the row's current best list,
@@ -80,9 +112,9 @@ __device__ __forceinline__ uint64_t compact_row(uint2* ent, int k, int c, int la
 
 // KC: list capacity the LDS is sized for (k <= KC); the LDS sets the blocks per CU (2 / 2 / 1 / 1 for
 // KC 16 / 32 / 64 / 128), which the register budget follows.  Block: 64 queries x one gallery span.
-template <int KC>
+template <int KC, typename GT>
 __global__ __launch_bounds__(256, KC <= 32 ? 2 : 1) void topk_partial_kernel(
-    const float* __restrict__ qry, const float* __restrict__ gal, int nq, int N, int E, float scale, float bias, int k,
+    const float* __restrict__ qry, const GT* __restrict__ gal, int nq, int N, int E, float scale, float bias, int k,
     int span_cols, int n_spans, uint2* __restrict__ ws) {
   constexpr int STRIDE = KC + CAND1;
   __shared__ __attribute__((aligned(16))) float stage[2][TB * LDT];  // A | B: [row][k slot qd][k step]
@@ -111,6 +143,12 @@ __global__ __launch_bounds__(256, KC <= 32 ? 2 : 1) void topk_partial_kernel(
     for (int p = 0; p < 4; ++p)
       v[p] = k0 + sj * 4 < E ? *(const float4*)(src[p] + k0) : make_float4(0.f, 0.f, 0.f, 0.f);
   };
+  // the gallery side stays as loaded (raw_t) until it is staged: widening it here would wait for the load
+  typedef typename GalRaw<GT>::type raw_t;
+  auto loadb = [&](raw_t(&v)[4], const GT* const(&src)[4], int k0) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) v[p] = k0 + sj * 4 < E ? gal_raw(src[p] + k0) : raw_t{};  // zero bits widen to 0.f
+  };
   auto put = [&](float* dst, const float4(&v)[4]) {
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
@@ -122,23 +160,29 @@ __global__ __launch_bounds__(256, KC <= 32 ? 2 : 1) void topk_partial_kernel(
 #pragma unroll
   for (int p = 0; p < 4; ++p) pa[p] = qry + (long)min(i0 + p * 16 + srow, nq - 1) * E + sj * 4;
   for (unsigned j0 = c_begin; j0 < c_end; j0 += TB) {
-    const float* pb[4];
+    const GT* pb[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) pb[p] = gal + (long)min(j0 + p * 16 + srow, (unsigned)N - 1) * E + sj * 4;
     f32x4 acc[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float4 va[4], vb[4];
+    float4 va[4];
+    raw_t vb[4];
     load(va, pa, 0);
-    load(vb, pb, 0);
+    loadb(vb, pb, 0);
     for (int k0 = 0; k0 < E; k0 += TK) {
       __syncthreads();
       put(stage[0], va);
-      put(stage[1], vb);
+      {
+        float4 wb[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) wb[p] = gal_widen<GT>(vb[p]);
+        put(stage[1], wb);
+      }
       __syncthreads();
       if (k0 + TK < E) {
         load(va, pa, k0 + TK);
-        load(vb, pb, k0 + TK);
+        loadb(vb, pb, k0 + TK);
       }
       const int steps = min(TK, E - k0) / 4;  // a multiple of 4 (E % 16 == 0): the last slab may be short
 #pragma unroll
@@ -216,22 +260,34 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const uint2* __restrict
   const int total = n_spans * k;
   uint64_t thr = 0;
   int c = 0;
-  for (int base = 0; base < total; base += 64) {
-    const int i = base + lane;
-    const uint2 e = i < total ? src[i] : ent_empty();
-    const uint64_t key = ent_key(e);
-    bool pass = key > thr;  // an empty entry (key 0) never passes
-    uint64_t bal = __ballot(pass);
-    if (bal == 0) continue;
-    if (c + __popcll(bal) > CAND2) {
-      thr = compact_row(ent, k, c, lane);
-      c = 0;
-      pass = key > thr;
-      bal = __ballot(pass);
+  // MS 64-entry steps are loaded at once: with few query rows this loop is one wave waiting on its own
+  // loads.  They are processed in the order they lie in, so the selection runs as it did one step a time.
+  // CLIPGPU_TOPK_MERGE_STEPS=1 (a variant build) is the one-step loop, for the A/B in DESIGN.md.
+  constexpr int MS = CLIPGPU_TOPK_MERGE_STEPS;
+  for (long base = 0; base < total; base += 64 * MS) {
+    uint2 e4[MS];
+#pragma unroll
+    for (int u = 0; u < MS; ++u) {
+      const long i = base + 64 * u + lane;
+      e4[u] = i < total ? src[i] : ent_empty();
     }
-    if (pass) ent[k + c + __popcll(bal & ((1ull << lane) - 1ull))] = e;
-    wave_lds_order();
-    c += __popcll(bal);
+#pragma unroll
+    for (int u = 0; u < MS; ++u) {
+      const uint2 e = e4[u];
+      const uint64_t key = ent_key(e);
+      bool pass = key > thr;  // an empty entry (key 0) never passes
+      uint64_t bal = __ballot(pass);
+      if (bal == 0) continue;
+      if (c + __popcll(bal) > CAND2) {
+        thr = compact_row(ent, k, c, lane);
+        c = 0;
+        pass = key > thr;
+        bal = __ballot(pass);
+      }
+      if (pass) ent[k + c + __popcll(bal & ((1ull << lane) - 1ull))] = e;
+      wave_lds_order();
+      c += __popcll(bal);
+    }
   }
   if (c > 0) compact_row(ent, k, c, lane);
   for (int t = lane; t < k; t += 64) {
@@ -242,37 +298,280 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const uint2* __restrict
   }
 }
 
-template <int KC>
-void launch_partial(const float* q, int nq, const float* g, int N, int E, float scale, float bias, int k,
-                    const TopkPlan& p, void* ws, hipStream_t s) {
-  hipLaunchKernelGGL(topk_partial_kernel<KC>, dim3((nq + TB - 1) / TB, p.n_spans), dim3(256), 0, s, q, g, nq, N, E,
-                     scale, bias, k, p.span_cols, p.n_spans, (uint2*)ws);
+// ---- few queries: at most 16 query rows per launch -------------------------------------------------
+// The wide kernel's 64-row query tile does 64 / nq times the MFMA work a few queries need, and its two
+// blocks per CU stream the gallery at a fraction of the HBM rate.  Here a block is ONE wave that owns a
+// 16-row query tile and a gallery span, walked in 16-column tiles: one 16x16 MFMA tile, the same
+// v_mfma_f32_16x16x4_f32 chain in the same k order through the same [k slot][k step] staging, so the
+// scores carry the wide kernel's bits.  There is no block barrier: the wave stages into LDS of its own
+// (11 KiB) and keeps its rows' selection state (16 x (KC + 32) entries), 17 - 32 KiB per block, so 9 to 5
+// waves per CU are resident.  Slabs of 64 k are requested two ahead, into registers, in one flat
+// sequence over (tile, slab): the loads of the next tile are in flight during this tile's MFMAs and
+// selection (up to 2 x 4 KiB of gallery per wave for f32, 2 x 2 KiB for 16-bit; see request() for what
+// the compiled loop keeps of it).  Query rows past nq are
+// clamped for the loads and never enter the selection.
+constexpr int NB = 16;
+
+template <int KC, typename GT>
+__global__ __launch_bounds__(64) void topk_narrow_kernel(const float* __restrict__ qry, const GT* __restrict__ gal,
+                                                         int nq, int N, int E, float scale, float bias, int k,
+                                                         int span_cols, int n_spans, uint2* __restrict__ ws) {
+  typedef typename GalRaw<GT>::type raw_t;
+  constexpr int STRIDE = KC + CAND1;
+  __shared__ __attribute__((aligned(16))) float stage[2][NB * LDT];  // A | B: [row][k slot qd][k step]
+  __shared__ uint2 sel[NB * STRIDE];
+  __shared__ int cnt[NB];
+  const int lane = threadIdx.x, span = blockIdx.x;
+  const unsigned c_begin = (unsigned)span * span_cols;  // < N
+  const unsigned c_end = min((unsigned)N, c_begin + span_cols);
+  for (int i = lane; i < NB * STRIDE; i += 64) sel[i] = ent_empty();
+  if (lane < NB) cnt[lane] = 0;
+  wave_lds_order();
+  const int r = lane & 15, qd = lane >> 4;
+  uint64_t thr[4] = {0, 0, 0, 0};  // thresholds of rows 4 * qd + e
+  // Staging as in the wide kernel, by one wave: lane -> (rows lane / 16 + 4 p, p < 4; k step lane % 16).
+  const int srow = lane >> 4, sj = lane & 15;
+  const float* pa[4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) pa[p] = qry + (long)min(p * 4 + srow, nq - 1) * E;
+  unsigned lj = c_begin;  // the next slab to request: tile lj, k lk
+  int lk = 0;
+  // Every request is the same eight loads, whatever the position, so that the compiler can count the
+  // loads in flight (with a conditional request it waits for all of them at every step).  In the ISA the
+  // second step of the pair below waits with eight loads left in flight (vmcnt(8)) and the first with
+  // six (f32) or four (16-bit): not the full slab there, because the compiler reorders the loads of the
+  // prologue, but no step waits for all of them any more.
+  // A lane whose k step lies past the end of E reads the
+  // row's last four elements instead (the MFMA loop never reads what it stages: it stops at E); past
+  // the end of the span the request reads the gallery's last rows again and nobody uses it.
+  auto request = [&](float4(&va)[4], raw_t(&vb)[4]) {
+    const int ko = min(lk + sj * 4, E - 4);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      va[p] = *(const float4*)(pa[p] + ko);
+      vb[p] = gal_raw(gal + (long)min(lj + p * 4 + srow, (unsigned)N - 1) * E + ko);
+    }
+    lk += TK;
+    if (lk >= E) {
+      lk = 0;
+      lj += NB;
+    }
+  };
+  auto put = [&](float* dst, int p, float4 v) {
+    float* d = dst + (p * 4 + srow) * LDT + sj;
+    d[0] = v.x; d[KQ] = v.y; d[2 * KQ] = v.z; d[3 * KQ] = v.w;
+  };
+  // C[row = 4 * qd + e][col = r] of the tile at column cj: the wide kernel's selection, on one column tile
+  auto select = [&](unsigned cj, const f32x4& acc) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (e >= nq) break;  // rows 4 * qd + e >= e: all padding
+      const unsigned col = cj + r;
+      const int rl = 4 * qd + e;
+      const uint32_t bits = __float_as_uint(fmaf(acc[e], scale, bias));
+      const uint64_t key = topk_key(bits, col);
+      const bool live = col < c_end && rl < nq;
+      bool pass = live && key > thr[e];
+      uint64_t bal = __ballot(pass);
+      if (bal == 0) continue;
+      unsigned mq = (unsigned)(bal >> (16 * qd)) & 0xffffu;
+      int c = cnt[rl];
+      if (__ballot(c + __popc(mq) > CAND1) != 0) {
+        for (int g = 0; g < 4; ++g) {  // the four rows this ballot covers
+          const int row = 4 * g + e;
+          const int c2 = cnt[row];
+          if (c2 + __popc((unsigned)(bal >> (16 * g)) & 0xffffu) > CAND1) {
+            const uint64_t t2 = compact_row(sel + row * STRIDE, k, c2, lane);
+            if (lane == 0) cnt[row] = 0;
+            if (qd == g) thr[e] = t2;
+          }
+        }
+        wave_lds_order();
+        pass = live && key > thr[e];
+        bal = __ballot(pass);
+        mq = (unsigned)(bal >> (16 * qd)) & 0xffffu;
+        c = cnt[rl];
+      }
+      if (pass) sel[rl * STRIDE + k + c + __popc(mq & ((1u << r) - 1u))] = make_uint2(bits, col);
+      wave_lds_order();
+      if (r == 0 && mq != 0) cnt[rl] = c + __popc(mq);
+      wave_lds_order();
+    }
+  };
+  unsigned cj = c_begin;  // the slab in hand: tile cj, k ck
+  int ck = 0;
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+  auto step = [&](float4(&va)[4], raw_t(&vb)[4]) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      put(stage[0], p, va[p]);
+      put(stage[1], p, gal_widen<GT>(vb[p]));
+    }
+    wave_lds_order();
+    request(va, vb);  // two slabs ahead; the slab after this one is already in flight
+    const int steps = min(TK, E - ck) / 4;  // a multiple of 4 (E % 16 == 0): the last slab may be short
+    // 16x16x4: lane (r, qd) supplies A[r][qd] and B[qd][r]; k = ck + 4 * (4 jq + st) + qd, ascending
+    const float* fa = &stage[0][r * LDT + qd * KQ];
+    const float* fb = &stage[1][r * LDT + qd * KQ];
+    if (steps == TK / 4) {  // a full slab: all eight fragment reads go out before the first MFMA waits
+      f32x4 a[4], b[4];
+#pragma unroll
+      for (int jq = 0; jq < 4; ++jq) {
+        a[jq] = *(const f32x4*)(fa + jq * 4);
+        b[jq] = *(const f32x4*)(fb + jq * 4);
+      }
+#pragma unroll
+      for (int jq = 0; jq < 4; ++jq)
+#pragma unroll
+        for (int st = 0; st < 4; ++st) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[jq][st], b[jq][st], acc, 0, 0, 0);
+    } else {
+#pragma unroll
+      for (int jq = 0; jq < 3; ++jq) {
+        if (jq * 4 >= steps) break;
+        const f32x4 a = *(const f32x4*)(fa + jq * 4);
+        const f32x4 b = *(const f32x4*)(fb + jq * 4);
+#pragma unroll
+        for (int st = 0; st < 4; ++st) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[st], b[st], acc, 0, 0, 0);
+      }
+    }
+    wave_lds_order();  // the fragment reads come before the next slab's stores
+    ck += TK;
+    if (ck >= E) {
+      select(cj, acc);
+      acc = f32x4{0.f, 0.f, 0.f, 0.f};
+      ck = 0;
+      cj += NB;
+    }
+  };
+  float4 a0[4] = {}, a1[4] = {};
+  raw_t b0[4] = {}, b1[4] = {};
+  // The steps run in pairs, a fixed number of them, with no exit between the two of a pair: with an exit
+  // there the compiler sees a path from one first step to the next without the second one's loads and
+  // waits for every load.  An odd count ends in one step past the span: it stages rows that request()
+  // clamped into the gallery, and if it completes a tile, every column of it is >= c_end and none passes.
+  // The barriers keep the two prologue requests apart, so that the first step's loads are the older ones.
+  request(a0, b0);
+  __builtin_amdgcn_sched_barrier(0);
+  request(a1, b1);
+  __builtin_amdgcn_sched_barrier(0);
+  const int n_steps = (int)((c_end - c_begin + NB - 1) / NB) * ((E + TK - 1) / TK);
+  for (int it = 0; it < n_steps; it += 2) {
+    step(a0, b0);
+    step(a1, b1);
+  }
+  for (int row = 0; row < nq; ++row) {
+    const int c2 = cnt[row];
+    if (c2 > 0) compact_row(sel + row * STRIDE, k, c2, lane);
+    uint2* dst = ws + ((long)row * n_spans + span) * k;
+    for (int t = lane; t < k; t += 64) dst[t] = sel[row * STRIDE + t];
+  }
 }
+
+template <int KC, typename GT>
+void launch_partial(bool narrow, const float* q, int nq, const void* g, int N, int E, float scale, float bias, int k,
+                    const TopkPlan& p, void* ws, hipStream_t s) {
+  if (narrow)
+    hipLaunchKernelGGL((topk_narrow_kernel<KC, GT>), dim3(p.n_spans), dim3(64), 0, s, q, (const GT*)g, nq, N, E, scale,
+                       bias, k, p.span_cols, p.n_spans, (uint2*)ws);
+  else
+    hipLaunchKernelGGL((topk_partial_kernel<KC, GT>), dim3((nq + TB - 1) / TB, p.n_spans), dim3(256), 0, s, q,
+                       (const GT*)g, nq, N, E, scale, bias, k, p.span_cols, p.n_spans, (uint2*)ws);
+}
+
+template <typename GT>
+void launch_partial_k(bool narrow, const float* q, int nq, const void* g, int N, int E, float scale, float bias, int k,
+                      const TopkPlan& p, void* ws, hipStream_t s) {
+  if (k <= 16) launch_partial<16, GT>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, s);
+  else if (k <= 32) launch_partial<32, GT>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, s);
+  else if (k <= 64) launch_partial<64, GT>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, s);
+  else launch_partial<128, GT>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, s);
+}
+
+// ---- 16-bit gallery rows: f32 -> storage (round to nearest even) and back (exact) -------------------
+__device__ __forceinline__ uint32_t round16(float x, _Float16*) {
+  const _Float16 h = (_Float16)x;  // v_cvt_f16_f32: nearest even, subnormals kept, |x| >= 65520 -> inf
+  return (uint32_t) __builtin_bit_cast(uint16_t, h);
+}
+__device__ __forceinline__ uint32_t round16(float x, __bf16*) {
+  const uint32_t b = __float_as_uint(x);
+  if ((b & 0x7fffffffu) > 0x7f800000u) return (b >> 16) | 0x40u;  // NaN stays NaN (quiet), sign kept
+  return (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;                    // carries into the exponent, up to inf
+}
+
+template <typename GT>
+__global__ __launch_bounds__(256) void gal_round_kernel(const float* __restrict__ in, GT* __restrict__ out, long n4) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const float4 v = ((const float4*)in)[i];
+    uint2 o;
+    o.x = round16(v.x, (GT*)nullptr) | (round16(v.y, (GT*)nullptr) << 16);
+    o.y = round16(v.z, (GT*)nullptr) | (round16(v.w, (GT*)nullptr) << 16);
+    ((uint2*)out)[i] = o;
+  }
+}
+
+template <typename GT>
+__global__ __launch_bounds__(256) void gal_widen_kernel(const GT* __restrict__ in, float* __restrict__ out, long n4) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256)
+    ((float4*)out)[i] = gal4(in + 4 * i);
+}
+
+int convert_blocks(long n4) { return (int)std::min<long>((n4 + 255) / 256, 8192); }
 
 }  // namespace
 
-TopkPlan topk_plan(long N, int q_tiles, int max_blocks) {
+int topk_gal_bytes(int dtype) { return dtype == TOPK_GAL_F32 ? 4 : 2; }
+
+hipError_t launch_gal_round(int dtype, const float* in, void* out, long n, hipStream_t s) {
+  if (n <= 0 || n % 4 || (dtype != TOPK_GAL_F16 && dtype != TOPK_GAL_BF16)) return hipErrorInvalidValue;
+  if (dtype == TOPK_GAL_F16)
+    hipLaunchKernelGGL(gal_round_kernel<_Float16>, dim3(convert_blocks(n / 4)), dim3(256), 0, s, in, (_Float16*)out, n / 4);
+  else
+    hipLaunchKernelGGL(gal_round_kernel<__bf16>, dim3(convert_blocks(n / 4)), dim3(256), 0, s, in, (__bf16*)out, n / 4);
+  return hipGetLastError();
+}
+
+hipError_t launch_gal_widen(int dtype, const void* in, float* out, long n, hipStream_t s) {
+  if (n <= 0 || n % 4 || (dtype != TOPK_GAL_F16 && dtype != TOPK_GAL_BF16)) return hipErrorInvalidValue;
+  if (dtype == TOPK_GAL_F16)
+    hipLaunchKernelGGL(gal_widen_kernel<_Float16>, dim3(convert_blocks(n / 4)), dim3(256), 0, s, (const _Float16*)in, out,
+                       n / 4);
+  else
+    hipLaunchKernelGGL(gal_widen_kernel<__bf16>, dim3(convert_blocks(n / 4)), dim3(256), 0, s, (const __bf16*)in, out,
+                       n / 4);
+  return hipGetLastError();
+}
+
+bool topk_narrow_route(int nq) {
+  const int route = g_topk_route.load();
+  if (route == 1 || nq > NB) return false;
+  return route == 2 || nq <= kNarrowRows;
+}
+
+TopkPlan topk_plan(long N, int nq, int max_blocks) {
   const long tiles = (N + TB - 1) / TB;
-  const long most = std::max(1L, (long)max_blocks / q_tiles);  // spans the workspace holds
+  TopkPlan p;
+  p.narrow = topk_narrow_route(nq);
+  // spans the workspace holds: it is sized for max_blocks blocks of 64 query rows, a narrow launch has 16
+  const long most = p.narrow ? std::min<long>(4L * max_blocks, kNarrowSpans) : std::max(1L, (long)max_blocks / ((nq + TB - 1) / TB));
   long want = std::min(tiles, most);
   const long forced = g_topk_span_cols.load();
   if (forced > 0) want = std::min(most, (tiles + forced / TB - 1) / (forced / TB));
-  TopkPlan p;
   p.span_cols = (int)((tiles + want - 1) / want) * TB;
   p.n_spans = (int)((N + p.span_cols - 1) / p.span_cols);
   return p;
 }
 
-hipError_t launch_topk(const float* q, int nq, const float* g, int N, int E, float scale, float bias, int k,
+hipError_t launch_topk(const float* q, int nq, const void* g, int dtype, int N, int E, float scale, float bias, int k,
                        const TopkPlan& p, void* ws, int64_t* out_idx, float* out_score, hipStream_t s) {
   if (nq <= 0 || N <= 0 || E <= 0 || E % 16 != 0 || k < 1 || k > kTopkMax) return hipErrorInvalidValue;
   if (p.span_cols <= 0 || p.span_cols % TB != 0 || (long)p.n_spans * p.span_cols < N ||
       (long)(p.n_spans - 1) * p.span_cols >= N || (long)p.n_spans * k > INT32_MAX || p.n_spans > 65535)
     return hipErrorInvalidValue;
-  if (k <= 16) launch_partial<16>(q, nq, g, N, E, scale, bias, k, p, ws, s);
-  else if (k <= 32) launch_partial<32>(q, nq, g, N, E, scale, bias, k, p, ws, s);
-  else if (k <= 64) launch_partial<64>(q, nq, g, N, E, scale, bias, k, p, ws, s);
-  else launch_partial<128>(q, nq, g, N, E, scale, bias, k, p, ws, s);
+  if (p.narrow && nq > NB) return hipErrorInvalidValue;
+  if (dtype == TOPK_GAL_F32) launch_partial_k<float>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, s);
+  else if (dtype == TOPK_GAL_F16) launch_partial_k<_Float16>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, s);
+  else if (dtype == TOPK_GAL_BF16) launch_partial_k<__bf16>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, s);
+  else return hipErrorInvalidValue;
   hipLaunchKernelGGL(topk_merge_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, (const uint2*)ws, nq, p.n_spans, k,
                      out_idx, out_score);
   return hipGetLastError();

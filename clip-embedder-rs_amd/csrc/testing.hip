@@ -405,6 +405,15 @@ int clipgpu_test_topk_span_cols(int64_t cols) {
   });
 }
 
+int clipgpu_test_topk_route(int route) {
+  return guarded([&]() {
+    if (route < 0 || route > 2) throw ClipErr(CLIPGPU_ERR_INVALID, "route must be 0 (default), 1 (wide) or 2 (few-query)");
+    g_topk_route.store(route);
+  });
+}
+
+int clipgpu_test_topk_narrow_rows(void) { return kNarrowRows; }
+
 int clipgpu_test_topk_key(float score, uint32_t index, uint64_t* key) {
   return guarded([&]() {
     if (!key) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL key");

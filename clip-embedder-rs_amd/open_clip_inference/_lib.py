@@ -56,6 +56,9 @@ _PROTOS = [
     ("clipgpu_similarity", c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_float, c_float, c_int, c_int, c_void_p]),
     ("clipgpu_similarity_device", c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_float, c_float, c_int, c_int, c_void_p, c_void_p]),
     ("clipgpu_index_create", c_int, [c_int, c_int64, c_int64, POINTER(c_void_p)]),
+    ("clipgpu_index_create_ex", c_int, [c_int, c_int64, c_int64, c_int, POINTER(c_void_p)]),
+    ("clipgpu_index_dtype", c_int, [c_void_p]),
+    ("clipgpu_index_get_rows", c_int, [c_void_p, c_int64, c_int64, c_void_p]),
     ("clipgpu_index_destroy", None, [c_void_p]),
     ("clipgpu_index_size", c_int64, [c_void_p]),
     ("clipgpu_index_clear", c_int, [c_void_p]),
@@ -83,6 +86,8 @@ _PROTOS = [
     ("clipgpu_test_gemm_mx_at", c_int, [c_int, c_int, c_int] + [c_int64] * 5 + [c_int] + [c_void_p] * 7),
     ("clipgpu_test_gemm_chunk_rows", c_int, [c_int64]),
     ("clipgpu_test_topk_span_cols", c_int, [c_int64]),
+    ("clipgpu_test_topk_route", c_int, [c_int]),
+    ("clipgpu_test_topk_narrow_rows", c_int, []),
     ("clipgpu_test_topk_key", c_int, [c_float, ctypes.c_uint32, POINTER(c_uint64)]),
     ("clipgpu_test_gemm_lnf", c_int, [c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_float, c_int, c_void_p]),

@@ -122,13 +122,14 @@ class Clip:
         return out
 
     # -- a gallery resident on the GPU, searched top-k (README.md:76-82, examples/search.rs) ----
-    def build_index(self, images, capacity=None):
+    def build_index(self, images, capacity=None, dtype="f32"):
         """Embeds ``images`` and stores them in an ``EmbeddingIndex`` on the vision engine's first
-        device (``capacity`` rows, default: as many as there are images); image i is index i."""
+        device (``capacity`` rows, default: as many as there are images; ``dtype`` "f32", "f16" or
+        "bf16": the index's storage type); image i is index i."""
         from .index import EmbeddingIndex
         embs = self.vision.embed_images(images)
         index = EmbeddingIndex(embs.shape[1], len(embs) if capacity is None else int(capacity),
-                               self.vision.session.devices[0])
+                               self.vision.session.devices[0], dtype)
         index.add(embs)
         return index
 

@@ -279,10 +279,44 @@ int clipgpu_similarity_device(const float* d_img, int64_t n_img, const float* d_
  * A handle serialises its callers (mutex).  The _device forms take device pointers on `device`, are
  * ordered on `stream` (NULL = the legacy default stream) and return without synchronising; the
  * handle also orders each operation after its previous one by an event, so an add on one stream
- * followed by a search on another sees the added rows.  The host forms synchronise. */
+ * followed by a search on another sees the added rows.  The host forms synchronise.
+ *
+ * Storage type (clipgpu_index_create_ex; clipgpu_index_create is CLIPGPU_INDEX_F32).  The memory
+ * follows the row bytes: a million 512-d rows are 2 GiB in f32 and 1 GiB in f16 / bf16.  The time
+ * does not yet: measured over 2^20 x 512 rows, one query takes 0.47 ms on f32 and 0.43 ms on f16 /
+ * bf16 (about 8 % less, not half), 16 queries take the same on all three, and so do 17 and more:
+ * the few-query kernel is bound by its staging through on-chip memory, not by reading the gallery,
+ * and the wide kernel by its arithmetic (embedding index).  Choose a 16-bit type for
+ * the memory.  add and add_device still take f32 rows (add_device: d_rows 16-byte aligned for a
+ * 16-bit index, whose convert kernel reads them four at a time; an F32 index copies them and asks
+ * only for f32 alignment); a 16-bit index rounds them on the device, round to nearest even: f16 keeps subnormals
+ * (2^-24 .. 2^-14) and sends |x| >= 65520 to +-inf (65504 is the largest finite value); bf16 keeps
+ * f32's exponent range; NaN stays NaN and -0.0 stays -0.0.  Queries stay f32 and the score is
+ * unchanged, fmaf(dot(q, widen(row)), scale, bias) on the same k-ascending exact-f32 chain
+ * (widening is exact): a 16-bit index returns exactly what an F32 index holding
+ * widen(round(rows)) returns, bit for bit.  Against the F32 index of the unrounded rows a logit
+ * moves by at most (derived, not measured)
+ *   |dscore| <= |scale| * u * sum_i |q_i g_i| <= |scale| * u * ||q|| ||g||,
+ *   u = 2^-11 (f16, normal range) or 2^-8 (bf16):
+ * 0.049 (f16) and 0.39 (bf16) at scale 100 on unit rows; the two f32 chains' own rounding adds
+ * about E * 2^-23 * sum_i |q_i g_i| on top.  clipgpu_index_get_rows copies rows [first, first + n)
+ * as stored, widened to f32, to host memory [n][E] (ordered after the handle's last operation; it
+ * synchronises): an export of the index, and the rounding made visible.  For a 16-bit index,
+ * clipgpu_index_add and clipgpu_index_get_rows pass the f32 rows through a device scratch buffer
+ * (at most 64 MiB) that the handle allocates at the first such call and keeps until it is destroyed.  first < 0, n <= 0 or
+ * first + n > size is CLIPGPU_ERR_INVALID; an unknown dtype is CLIPGPU_ERR_INVALID "unknown index
+ * dtype", raised like the other create-time errors before any device call.
+ *
+ * Few queries: a launch of at most 16 query rows (the last chunk of any call included) may run a
+ * few-query kernel instead of the 64-row-tile one.  The results are bit-identical; the route shows
+ * only in the time (embedding index, has the measured threshold). */
 typedef struct clipgpu_index clipgpu_index;
 #define CLIPGPU_TOPK_MAX 128
+enum clipgpu_index_dtype { CLIPGPU_INDEX_F32 = 0, CLIPGPU_INDEX_F16 = 1, CLIPGPU_INDEX_BF16 = 2 };
 int clipgpu_index_create(int device, int64_t E, int64_t capacity, clipgpu_index** out);
+int clipgpu_index_create_ex(int device, int64_t E, int64_t capacity, int dtype, clipgpu_index** out);
+int clipgpu_index_dtype(const clipgpu_index* ix); /* the enum; -1 for NULL */
+int clipgpu_index_get_rows(clipgpu_index* ix, int64_t first, int64_t n, float* out_rows); /* host [n][E] */
 void clipgpu_index_destroy(clipgpu_index* ix);
 int64_t clipgpu_index_size(const clipgpu_index* ix); /* rows added so far */
 int clipgpu_index_clear(clipgpu_index* ix);          /* size 0; the capacity stays */

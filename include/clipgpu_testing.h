@@ -265,6 +265,15 @@ int clipgpu_test_gather_plan(int nranks, const int64_t* rows, int64_t* off, int*
  * fills the GPU), process-wide and atomic, for every search started afterwards: small galleries then
  * run many spans and the merge.  The result never depends on it. */
 int clipgpu_test_topk_span_cols(int64_t cols);
+/* Which phase-1 kernel a search launch runs, process-wide and atomic, for every search started
+ * afterwards: 0 = the default dispatch (at most kNarrowRows query rows: the few-query kernel), 1 = always
+ * the wide kernel, 2 = the few-query kernel for every launch of at most 16 rows.  Other values are
+ * refused.  The result never depends on it; tests run both kernels on one input with it and the
+ * benchmark times them in one process. */
+int clipgpu_test_topk_route(int route);
+/* Host only: kNarrowRows, the largest number of query rows a launch sends to the few-query kernel on
+ * the default dispatch (1 .. 16). */
+int clipgpu_test_topk_narrow_rows(void);
 /* Host only: the search's order key (csrc/kernels/topk_key.hpp) of (score, gallery index): a larger
  * key ranks first. */
 int clipgpu_test_topk_key(float score, uint32_t index, uint64_t* key);

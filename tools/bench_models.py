@@ -163,14 +163,107 @@ def similarity_leg(ni=65536, nt=1000, E=512, steps=5, warmup=2):
                       "max_abs_err_vs_torch": err}), flush=True)
 
 
-def topk_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2):
-    """Semantic search over a device-resident gallery of N embeddings, Q = 256 and Q = 1 queries:
-    the fused top-k search (clipgpu_index_search_device) against the same result by the full-matrix
-    path (clipgpu_similarity_device logits into a [Q][N] tensor, then torch.topk on the device).  The
-    two alternate in one process; per path the median and the spread of `runs` device-event timings
-    after `warmup` rounds.  Both do 2 Q N E f32-MFMA FLOP; the fused path's floor is the larger of
-    that over the f32 MFMA peak (157.3 TF) and one read of the gallery over the HBM peak (8 TB/s)."""
+INDEX_DTYPES = {"f32": (4, None), "f16": (2, torch.float16), "bf16": (2, torch.bfloat16)}
+
+
+def _event_ms(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def _stats(v, nbytes):
+    med = float(np.median(v))
+    return {"ms_median": round(med, 3), "ms_min_max": [round(min(v), 3), round(max(v), 3)],
+            "gallery_TBps": round(nbytes / (med * 1e-3) / 1e12, 2)}
+
+
+def topk_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 4, 16, 17, 32, 256), dtypes=("f32", "f16", "bf16")):
+    """Semantic search over a device-resident gallery of N embeddings, per query count and index storage
+    type: three legs alternate in one process -- the fused search on its default route
+    (clipgpu_index_search_device: the few-query kernel up to kNarrowRows query rows), the fused search
+    forced onto the wide kernel (clipgpu_test_topk_route 1: the only kernel before the few-query one
+    existed), and the same result by the full-matrix path (clipgpu_similarity_device logits into a
+    [Q][N] tensor, then torch.topk), which for a 16-bit index runs on the widened rounded gallery.  Per
+    leg the median and the spread of `runs` device-event timings after `warmup` rounds (the order of
+    the legs rotates from round to round: what a leg finds in the caches depends on the leg before it), and the
+    effective gallery bandwidth N E elem / t; the floor beside them is one read of the gallery at
+    6.3 TB/s.  All three legs return the same indices and bit-equal scores.  For the 16-bit types the
+    line also carries the top-k overlap with the F32 index (a Gaussian gallery, not embedding data)."""
     import ctypes
+    from open_clip_inference import EmbeddingIndex
+    torch.manual_seed(0)
+    L = _lib.lib()
+    s = torch.cuda.current_stream().cuda_stream
+    g = torch.nn.functional.normalize(torch.randn(N, E, device="cuda"), dim=1)
+    qs = {Q: torch.nn.functional.normalize(torch.randn(Q, E, device="cuda"), dim=1) for Q in Qs}
+    f32_idx = {}
+    try:
+        for dt in dtypes:
+            esz, tdt = INDEX_DTYPES[dt]
+            gw = g if tdt is None else g.to(tdt).float()  # what the index holds, widened
+            ix = EmbeddingIndex(E, N, dtype=dt)
+            ix.add_device(g.data_ptr(), N, s)
+            for Q in Qs:
+                q = qs[Q]
+                mat = torch.empty(Q, N, device="cuda")
+                res = {name: (torch.empty((Q, k), dtype=torch.int64, device="cuda"), torch.empty((Q, k), device="cuda"))
+                       for name in ("default", "wide")}
+                base = {}
+
+                def fused(name, route):
+                    _lib.check(L.clipgpu_test_topk_route(route))
+                    ix.search_device(q.data_ptr(), Q, k, res[name][0].data_ptr(), res[name][1].data_ptr(), 100.0, 0.0, s)
+
+                def baseline():
+                    _lib.check(L.clipgpu_similarity_device(ctypes.c_void_p(q.data_ptr()), Q, ctypes.c_void_p(gw.data_ptr()),
+                                                           N, E, 100.0, 0.0, 2, 1, ctypes.c_void_p(mat.data_ptr()),
+                                                           ctypes.c_void_p(s)))
+                    base["score"], base["idx"] = torch.topk(mat, k, dim=1)
+
+                legs = (("default", lambda: fused("default", 0)), ("wide", lambda: fused("wide", 1)), ("baseline", baseline))
+                ms = {name: [] for name, _ in legs}
+                for rnd in range(warmup + runs):
+                    for name, fn in legs[rnd % 3:] + legs[:rnd % 3]:  # every leg follows every other equally often
+                        t = _event_ms(fn)
+                        if rnd >= warmup:
+                            ms[name].append(t)
+                # the same result: scores bit for bit; indices once the baseline's ties are put in index order
+                b_idx, b_score = base["idx"].cpu().numpy(), base["score"].cpu().numpy()
+                order = np.lexsort((b_idx, -b_score.astype(np.float64)), axis=1)
+                b_idx, b_score = np.take_along_axis(b_idx, order, 1), np.take_along_axis(b_score, order, 1)
+                for name in ("default", "wide"):
+                    assert np.array_equal(res[name][1].cpu().numpy().view(np.uint32), b_score.view(np.uint32)), name
+                    assert np.array_equal(res[name][0].cpu().numpy(), b_idx), name
+                nbytes = N * E * esz
+                out = {"measure": "topk_search", "Q": Q, "dtype": dt, "N": N, "E": E, "k": k, "runs": runs,
+                       "same_indices": True, "gallery_read_floor_ms_at_6.3TBps": round(nbytes / 6.3e12 * 1e3, 3),
+                       "mfma_floor_ms_wide": round(2.0 * max(Q, 64) * N * E / 157.3e12 * 1e3, 3)}
+                for name, v in ms.items():
+                    out[name] = _stats(v, nbytes)
+                out["default_over_wide"] = round(out["default"]["ms_median"] / out["wide"]["ms_median"], 3)
+                out["default_over_baseline"] = round(out["default"]["ms_median"] / out["baseline"]["ms_median"], 3)
+                if dt == "f32":
+                    f32_idx[Q] = b_idx
+                elif Q in f32_idx:
+                    both = [len(set(a) & set(b)) for a, b in zip(b_idx.tolist(), f32_idx[Q].tolist())]
+                    out["topk_overlap_with_f32"] = round(float(np.mean(both)) / k, 4)
+                print(json.dumps(out), flush=True)
+            ix.close()
+    finally:
+        _lib.check(L.clipgpu_test_topk_route(0))
+
+
+def topk_routes_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 2, 4, 8, 12, 16)):
+    """The measurement kNarrowRows (csrc/kernels/kernels.hpp) is set by: for every query count the
+    few-query kernel can take, that kernel (route 2) against the wide one (route 1) on an f32 gallery,
+    alternating in one process in a fixed order (each leg always follows the other; swapping the order
+    from round to round would run a leg right after itself, on a gallery tail still in the cache, and
+    measured 0.675 instead of 0.76 ms at Q = 16); kNarrowRows is the largest Q at which the few-query
+    median is lower."""
     from open_clip_inference import EmbeddingIndex
     torch.manual_seed(0)
     L = _lib.lib()
@@ -178,51 +271,29 @@ def topk_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2):
     g = torch.nn.functional.normalize(torch.randn(N, E, device="cuda"), dim=1)
     ix = EmbeddingIndex(E, N)
     ix.add_device(g.data_ptr(), N, s)
-    for Q in (256, 1):
-        q = torch.nn.functional.normalize(torch.randn(Q, E, device="cuda"), dim=1)
-        mat = torch.empty(Q, N, device="cuda")
-        f_idx = torch.empty((Q, k), dtype=torch.int64, device="cuda")
-        f_score = torch.empty((Q, k), device="cuda")
-        base = {}
+    try:
+        for Q in Qs:
+            q = torch.nn.functional.normalize(torch.randn(Q, E, device="cuda"), dim=1)
+            res = {r: (torch.empty((Q, k), dtype=torch.int64, device="cuda"), torch.empty((Q, k), device="cuda"))
+                   for r in (1, 2)}
 
-        def fused():
-            ix.search_device(q.data_ptr(), Q, k, f_idx.data_ptr(), f_score.data_ptr(), 100.0, 0.0, s)
+            def run(r):
+                _lib.check(L.clipgpu_test_topk_route(r))
+                ix.search_device(q.data_ptr(), Q, k, res[r][0].data_ptr(), res[r][1].data_ptr(), 100.0, 0.0, s)
 
-        def baseline():
-            _lib.check(L.clipgpu_similarity_device(ctypes.c_void_p(q.data_ptr()), Q, ctypes.c_void_p(g.data_ptr()), N,
-                                                   E, 100.0, 0.0, 2, 1, ctypes.c_void_p(mat.data_ptr()),
-                                                   ctypes.c_void_p(s)))
-            base["score"], base["idx"] = torch.topk(mat, k, dim=1)
-
-        ms = {"fused": [], "baseline": []}
-        for rnd in range(warmup + runs):
-            for name, fn in (("fused", fused), ("baseline", baseline)):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                e1.synchronize()
-                if rnd >= warmup:
-                    ms[name].append(e0.elapsed_time(e1))
-        # the same result: scores bit for bit; indices once the baseline's ties are put in index order
-        b_idx, b_score = base["idx"].cpu().numpy(), base["score"].cpu().numpy()
-        order = np.lexsort((b_idx, -b_score.astype(np.float64)), axis=1)
-        b_idx, b_score = np.take_along_axis(b_idx, order, 1), np.take_along_axis(b_score, order, 1)
-        assert np.array_equal(f_score.cpu().numpy().view(np.uint32), b_score.view(np.uint32)), "scores differ"
-        assert np.array_equal(f_idx.cpu().numpy(), b_idx), "indices differ"
-        flop = 2.0 * Q * N * E
-        t_mfma, t_hbm = flop / 157.3e12, N * E * 4 / 8.0e12
-        out = {"measure": "topk_search", "Q": Q, "N": N, "E": E, "k": k, "runs": runs, "same_indices": True,
-               "fused_floor": "MFMA-bound" if t_mfma >= t_hbm else "HBM-bound",
-               "fused_floor_ms": round(max(t_mfma, t_hbm) * 1e3, 3)}
-        for name, v in ms.items():
-            med = float(np.median(v))
-            out[name + "_ms_median"] = round(med, 3)
-            out[name + "_ms_min_max"] = [round(min(v), 3), round(max(v), 3)]
-            out[name + "_tflops_f32"] = round(flop / (med * 1e-3) / 1e12, 2)
-        out["fused_speedup"] = round(out["baseline_ms_median"] / out["fused_ms_median"], 2)
-        print(json.dumps(out), flush=True)
-    ix.close()
+            ms = {1: [], 2: []}
+            for rnd in range(warmup + runs):
+                for r in (2, 1):  # a fixed order: with two legs a swapped order makes a leg follow itself
+                    t = _event_ms(lambda: run(r))
+                    if rnd >= warmup:
+                        ms[r].append(t)
+            assert torch.equal(res[1][0], res[2][0]) and torch.equal(res[1][1].view(torch.int32), res[2][1].view(torch.int32))
+            print(json.dumps({"measure": "topk_routes", "Q": Q, "N": N, "E": E, "k": k, "few_query": _stats(ms[2], N * E * 4),
+                              "wide": _stats(ms[1], N * E * 4),
+                              "few_query_over_wide": round(float(np.median(ms[2]) / np.median(ms[1])), 3)}), flush=True)
+    finally:
+        _lib.check(L.clipgpu_test_topk_route(0))
+        ix.close()
 
 
 def latency_leg(steps=50, warmup=10):
@@ -270,6 +341,8 @@ if __name__ == "__main__":
         latency_leg()
     if "topk" in which:  # the embedding index's fused search vs similarity + torch.topk
         topk_leg()
+    if "topkroutes" in which:  # the few-query kernel vs the wide one per query count: sets kNarrowRows
+        topk_routes_leg()
     if "so400m" in which:
         device_leg("so400m_vision", SO400M_16_SIGLIP2_384_CFG, 0, 128)
     if "h14" in which:
