@@ -214,8 +214,20 @@ struct TopkPlan { int span_cols, n_spans; bool narrow; };
 extern std::atomic<long> g_topk_span_cols;
 extern std::atomic<int> g_topk_route;
 TopkPlan topk_plan(long N, int nq, int max_blocks);
+// mask: NULL (every row, the unmasked kernels) or the filter bitmap of launch_topk_mask (the MASKED
+// kernels): only rows whose bit is set enter a result, out slots beyond min(k, allowed rows) are (-1, -inf).
 hipError_t launch_topk(const float* q, int nq, const void* g, int dtype, int N, int E, float scale, float bias, int k,
-                       const TopkPlan& p, void* ws, int64_t* out_idx, float* out_score, hipStream_t s);
+                       const TopkPlan& p, void* ws, const uint32_t* mask, int64_t* out_idx, float* out_score,
+                       hipStream_t s);
+// The filter bitmap the MASKED kernels read: row i is allowed iff bit i & 31 of word i >> 5 is set.
+// eff (8-byte aligned, topk_mask_words(n) words: whole 64-column tiles) = live & allow over rows [0, n),
+// bits >= n cleared.  live / allow: device words, NULL = all ones, read in their first ceil(n / 32) words;
+// allow may be eff itself.
+long topk_mask_words(long n);
+hipError_t launch_topk_mask(const uint32_t* live, const uint32_t* allow, uint32_t* eff, long n, hipStream_t s);
+// Row i of in (f32 [n][E], 16-byte aligned) -> row ids[i] of the gallery, rounded as launch_gal_round
+// rounds (an f32 gallery takes the bits).  ids: device, distinct, inside the gallery.
+hipError_t launch_gal_scatter(int dtype, const float* in, const int64_t* ids, void* gal, long n, int E, hipStream_t s);
 
 // out[r] = in[r] / max(||in[r]||_2, 1e-12)
 hipError_t launch_l2norm(const float* in, float* out, int B, int E, hipStream_t s);

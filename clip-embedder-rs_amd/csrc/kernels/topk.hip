@@ -23,6 +23,13 @@
 // The gallery is stored as f32, f16 or bf16 (TopkGal); a 16-bit element is widened in registers, which
 // is exact, so the dot products run on the same f32 chain over widen(row).  A chunk of at most 16 query
 // rows may take the few-query phase 1 instead (topk_narrow_kernel, below): same bits, same order.
+//
+// Filtered search (MASKED instantiations of both phase-1 kernels): a device bitmap of uint32 words, row i
+// allowed iff bit i & 31 of word i >> 5 is set, padded with zeros to whole 64-column tiles and 8-byte
+// aligned (mask_eff_kernel builds it: live rows AND the caller's allow bits, bits >= N cleared).  A
+// column whose bit is clear does not pass the ballot, so it never enters a list -- unlike a NaN score,
+// which ranks below -inf but is an entry.  A span with no allowed row hands the merge k empty entries.
+// The MASKED = false instantiations are the kernels as they were: an unfiltered search launches them.
 #include <algorithm>
 #include <atomic>
 #include <cstdint>
@@ -112,10 +119,10 @@ __device__ __forceinline__ uint64_t compact_row(uint2* ent, int k, int c, int la
 
 // KC: list capacity the LDS is sized for (k <= KC); the LDS sets the blocks per CU (2 / 2 / 1 / 1 for
 // KC 16 / 32 / 64 / 128), which the register budget follows.  Block: 64 queries x one gallery span.
-template <int KC, typename GT>
+template <int KC, typename GT, bool MASKED>
 __global__ __launch_bounds__(256, KC <= 32 ? 2 : 1) void topk_partial_kernel(
     const float* __restrict__ qry, const GT* __restrict__ gal, int nq, int N, int E, float scale, float bias, int k,
-    int span_cols, int n_spans, uint2* __restrict__ ws) {
+    int span_cols, int n_spans, uint2* __restrict__ ws, const uint2* __restrict__ mask) {
   constexpr int STRIDE = KC + CAND1;
   __shared__ __attribute__((aligned(16))) float stage[2][TB * LDT];  // A | B: [row][k slot qd][k step]
   __shared__ uint2 sel[TB * STRIDE];
@@ -126,6 +133,20 @@ __global__ __launch_bounds__(256, KC <= 32 ? 2 : 1) void topk_partial_kernel(
   // columns as unsigned: N < 2^31, but the last tile's padding columns may reach 2^31
   const unsigned c_begin = (unsigned)span * span_cols;  // < N
   const unsigned c_end = min((unsigned)N, c_begin + span_cols);
+  if constexpr (MASKED) {
+    // mask[t]: the two words of 64-column tile t.  A span with no allowed row (block-uniform): k empty
+    // entries per query row, nothing staged.
+    unsigned any = 0;
+    for (unsigned t = (c_begin >> 6) + tid; t < ((c_end + 63) >> 6); t += 256) any |= mask[t].x | mask[t].y;
+    if (!__syncthreads_or((int)(any != 0))) {
+      for (int row = wave * 16; row < wave * 16 + 16; ++row)
+        if (i0 + row < nq) {
+          uint2* dst = ws + ((long)(i0 + row) * n_spans + span) * k;
+          for (int t = lane; t < k; t += 64) dst[t] = ent_empty();
+        }
+      return;
+    }
+  }
   for (int i = tid; i < TB * STRIDE; i += 256) sel[i] = ent_empty();
   if (tid < TB) cnt[tid] = 0;
   __syncthreads();
@@ -160,6 +181,11 @@ __global__ __launch_bounds__(256, KC <= 32 ? 2 : 1) void topk_partial_kernel(
 #pragma unroll
   for (int p = 0; p < 4; ++p) pa[p] = qry + (long)min(i0 + p * 16 + srow, nq - 1) * E + sj * 4;
   for (unsigned j0 = c_begin; j0 < c_end; j0 += TB) {
+    uint2 mw = make_uint2(0, 0);  // the tile's allowed bits: columns j0 .. j0 + 31 | j0 + 32 .. j0 + 63
+    if constexpr (MASKED) {
+      mw = mask[j0 >> 6];
+      if ((mw.x | mw.y) == 0) continue;  // block-uniform, before the tile's loads and barriers
+    }
     const GT* pb[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p) pb[p] = gal + (long)min(j0 + p * 16 + srow, (unsigned)N - 1) * E + sj * 4;
@@ -207,7 +233,9 @@ __global__ __launch_bounds__(256, KC <= 32 ? 2 : 1) void topk_partial_kernel(
         const unsigned col = j0 + t * 16 + r;
         const uint32_t bits = __float_as_uint(fmaf(acc[t][e], scale, bias));
         const uint64_t key = topk_key(bits, col);
-        bool pass = col < c_end && key > thr[e];
+        bool ok = col < c_end;
+        if constexpr (MASKED) ok = ok && (((t < 2 ? mw.x : mw.y) >> ((t & 1) * 16 + r)) & 1u) != 0;
+        bool pass = ok && key > thr[e];
         uint64_t bal = __ballot(pass);
         if (bal == 0) continue;  // wave-uniform: the common case once the thresholds have warmed up
         const int rl = rowbase + 4 * qd + e;
@@ -224,7 +252,7 @@ __global__ __launch_bounds__(256, KC <= 32 ? 2 : 1) void topk_partial_kernel(
             }
           }
           wave_lds_order();
-          pass = col < c_end && key > thr[e];
+          pass = ok && key > thr[e];
           bal = __ballot(pass);
           mq = (unsigned)(bal >> (16 * qd)) & 0xffffu;
           c = cnt[rl];
@@ -310,12 +338,19 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const uint2* __restrict
 // selection (up to 2 x 4 KiB of gallery per wave for f32, 2 x 2 KiB for 16-bit; see request() for what
 // the compiled loop keeps of it).  Query rows past nq are
 // clamped for the loads and never enter the selection.
+//
+// MASKED: the allowed bits of a 16-column tile are half a mask word.  Every request carries one more
+// load, the word of the tile it requests (a request is still the same loads whatever the position), so
+// the word arrives with the tile's last slab and the selection starts no load of its own.  A tile is
+// never skipped -- a conditional request would end the counting of the loads in flight; only a span
+// with no allowed row leaves at once.
 constexpr int NB = 16;
 
-template <int KC, typename GT>
+template <int KC, typename GT, bool MASKED>
 __global__ __launch_bounds__(64) void topk_narrow_kernel(const float* __restrict__ qry, const GT* __restrict__ gal,
                                                          int nq, int N, int E, float scale, float bias, int k,
-                                                         int span_cols, int n_spans, uint2* __restrict__ ws) {
+                                                         int span_cols, int n_spans, uint2* __restrict__ ws,
+                                                         const uint32_t* __restrict__ mask) {
   typedef typename GalRaw<GT>::type raw_t;
   constexpr int STRIDE = KC + CAND1;
   __shared__ __attribute__((aligned(16))) float stage[2][NB * LDT];  // A | B: [row][k slot qd][k step]
@@ -324,6 +359,17 @@ __global__ __launch_bounds__(64) void topk_narrow_kernel(const float* __restrict
   const int lane = threadIdx.x, span = blockIdx.x;
   const unsigned c_begin = (unsigned)span * span_cols;  // < N
   const unsigned c_end = min((unsigned)N, c_begin + span_cols);
+  if constexpr (MASKED) {  // a span with no allowed row: k empty entries per query row, nothing requested
+    unsigned any = 0;
+    for (unsigned w = (c_begin >> 5) + lane; w < ((c_end + 63) >> 6) * 2; w += 64) any |= mask[w];
+    if (__ballot(any != 0) == 0) {
+      for (int row = 0; row < nq; ++row) {
+        uint2* dst = ws + ((long)row * n_spans + span) * k;
+        for (int t = lane; t < k; t += 64) dst[t] = ent_empty();
+      }
+      return;
+    }
+  }
   for (int i = lane; i < NB * STRIDE; i += 64) sel[i] = ent_empty();
   if (lane < NB) cnt[lane] = 0;
   wave_lds_order();
@@ -344,8 +390,12 @@ __global__ __launch_bounds__(64) void topk_narrow_kernel(const float* __restrict
   // A lane whose k step lies past the end of E reads the
   // row's last four elements instead (the MFMA loop never reads what it stages: it stops at E); past
   // the end of the span the request reads the gallery's last rows again and nobody uses it.
-  auto request = [&](float4(&va)[4], raw_t(&vb)[4]) {
+  auto request = [&](float4(&va)[4], raw_t(&vb)[4], uint32_t& vm) {
     const int ko = min(lk + sj * 4, E - 4);
+    // The word of tile lj, first: the oldest load of the request.  lj + 4 * srow lies in the tile, so
+    // every lane reads the same word; formed from the lane's row the address is not uniform to the
+    // compiler and the load is a vector load, counted with the eight below.
+    if constexpr (MASKED) vm = mask[min(lj + 4 * srow, (unsigned)N - 1) >> 5];
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       va[p] = *(const float4*)(pa[p] + ko);
@@ -362,7 +412,7 @@ __global__ __launch_bounds__(64) void topk_narrow_kernel(const float* __restrict
     d[0] = v.x; d[KQ] = v.y; d[2 * KQ] = v.z; d[3 * KQ] = v.w;
   };
   // C[row = 4 * qd + e][col = r] of the tile at column cj: the wide kernel's selection, on one column tile
-  auto select = [&](unsigned cj, const f32x4& acc) {
+  auto select = [&](unsigned cj, const f32x4& acc, bool allowed) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       if (e >= nq) break;  // rows 4 * qd + e >= e: all padding
@@ -370,7 +420,7 @@ __global__ __launch_bounds__(64) void topk_narrow_kernel(const float* __restrict
       const int rl = 4 * qd + e;
       const uint32_t bits = __float_as_uint(fmaf(acc[e], scale, bias));
       const uint64_t key = topk_key(bits, col);
-      const bool live = col < c_end && rl < nq;
+      const bool live = col < c_end && rl < nq && allowed;
       bool pass = live && key > thr[e];
       uint64_t bal = __ballot(pass);
       if (bal == 0) continue;
@@ -401,14 +451,25 @@ __global__ __launch_bounds__(64) void topk_narrow_kernel(const float* __restrict
   unsigned cj = c_begin;  // the slab in hand: tile cj, k ck
   int ck = 0;
   f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-  auto step = [&](float4(&va)[4], raw_t(&vb)[4]) {
+  auto step = [&](float4(&va)[4], raw_t(&vb)[4], uint32_t& vm) {
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       put(stage[0], p, va[p]);
       put(stage[1], p, gal_widen<GT>(vb[p]));
     }
+    // The bit of column cj + r (the tile is the low or the high half of its word), taken here: the word
+    // arrived before the rows just staged, and its register is free again for the request below.  Held
+    // across the request instead, the word's next value needs a second register and a copy at the end of
+    // the loop, which waits for every load.
+    // (The empty asm keeps the compiler from moving the shift down to the selection, past the request.)
+    uint32_t mbit = 1;
+    if constexpr (MASKED) {
+      mbit = (vm >> ((cj & 16) + r)) & 1u;
+      asm volatile("" : "+v"(mbit));
+    }
+    const bool allowed = mbit != 0;
     wave_lds_order();
-    request(va, vb);  // two slabs ahead; the slab after this one is already in flight
+    request(va, vb, vm);  // two slabs ahead; the slab after this one is already in flight
     const int steps = min(TK, E - ck) / 4;  // a multiple of 4 (E % 16 == 0): the last slab may be short
     // 16x16x4: lane (r, qd) supplies A[r][qd] and B[qd][r]; k = ck + 4 * (4 jq + st) + qd, ascending
     const float* fa = &stage[0][r * LDT + qd * KQ];
@@ -437,7 +498,7 @@ __global__ __launch_bounds__(64) void topk_narrow_kernel(const float* __restrict
     wave_lds_order();  // the fragment reads come before the next slab's stores
     ck += TK;
     if (ck >= E) {
-      select(cj, acc);
+      select(cj, acc, allowed);
       acc = f32x4{0.f, 0.f, 0.f, 0.f};
       ck = 0;
       cj += NB;
@@ -445,19 +506,20 @@ __global__ __launch_bounds__(64) void topk_narrow_kernel(const float* __restrict
   };
   float4 a0[4] = {}, a1[4] = {};
   raw_t b0[4] = {}, b1[4] = {};
+  uint32_t m0 = 0, m1 = 0;
   // The steps run in pairs, a fixed number of them, with no exit between the two of a pair: with an exit
   // there the compiler sees a path from one first step to the next without the second one's loads and
   // waits for every load.  An odd count ends in one step past the span: it stages rows that request()
   // clamped into the gallery, and if it completes a tile, every column of it is >= c_end and none passes.
   // The barriers keep the two prologue requests apart, so that the first step's loads are the older ones.
-  request(a0, b0);
+  request(a0, b0, m0);
   __builtin_amdgcn_sched_barrier(0);
-  request(a1, b1);
+  request(a1, b1, m1);
   __builtin_amdgcn_sched_barrier(0);
   const int n_steps = (int)((c_end - c_begin + NB - 1) / NB) * ((E + TK - 1) / TK);
   for (int it = 0; it < n_steps; it += 2) {
-    step(a0, b0);
-    step(a1, b1);
+    step(a0, b0, m0);
+    step(a1, b1, m1);
   }
   for (int row = 0; row < nq; ++row) {
     const int c2 = cnt[row];
@@ -467,24 +529,46 @@ __global__ __launch_bounds__(64) void topk_narrow_kernel(const float* __restrict
   }
 }
 
-template <int KC, typename GT>
+template <int KC, typename GT, bool MASKED>
 void launch_partial(bool narrow, const float* q, int nq, const void* g, int N, int E, float scale, float bias, int k,
-                    const TopkPlan& p, void* ws, hipStream_t s) {
+                    const TopkPlan& p, void* ws, const uint32_t* mask, hipStream_t s) {
   if (narrow)
-    hipLaunchKernelGGL((topk_narrow_kernel<KC, GT>), dim3(p.n_spans), dim3(64), 0, s, q, (const GT*)g, nq, N, E, scale,
-                       bias, k, p.span_cols, p.n_spans, (uint2*)ws);
+    hipLaunchKernelGGL((topk_narrow_kernel<KC, GT, MASKED>), dim3(p.n_spans), dim3(64), 0, s, q, (const GT*)g, nq, N,
+                       E, scale, bias, k, p.span_cols, p.n_spans, (uint2*)ws, mask);
   else
-    hipLaunchKernelGGL((topk_partial_kernel<KC, GT>), dim3((nq + TB - 1) / TB, p.n_spans), dim3(256), 0, s, q,
-                       (const GT*)g, nq, N, E, scale, bias, k, p.span_cols, p.n_spans, (uint2*)ws);
+    hipLaunchKernelGGL((topk_partial_kernel<KC, GT, MASKED>), dim3((nq + TB - 1) / TB, p.n_spans), dim3(256), 0, s, q,
+                       (const GT*)g, nq, N, E, scale, bias, k, p.span_cols, p.n_spans, (uint2*)ws, (const uint2*)mask);
+}
+
+template <typename GT, bool MASKED>
+void launch_partial_k(bool narrow, const float* q, int nq, const void* g, int N, int E, float scale, float bias, int k,
+                      const TopkPlan& p, void* ws, const uint32_t* mask, hipStream_t s) {
+  if (k <= 16) launch_partial<16, GT, MASKED>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, s);
+  else if (k <= 32) launch_partial<32, GT, MASKED>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, s);
+  else if (k <= 64) launch_partial<64, GT, MASKED>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, s);
+  else launch_partial<128, GT, MASKED>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, s);
 }
 
 template <typename GT>
-void launch_partial_k(bool narrow, const float* q, int nq, const void* g, int N, int E, float scale, float bias, int k,
-                      const TopkPlan& p, void* ws, hipStream_t s) {
-  if (k <= 16) launch_partial<16, GT>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, s);
-  else if (k <= 32) launch_partial<32, GT>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, s);
-  else if (k <= 64) launch_partial<64, GT>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, s);
-  else launch_partial<128, GT>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, s);
+void launch_partial_m(bool narrow, const float* q, int nq, const void* g, int N, int E, float scale, float bias, int k,
+                      const TopkPlan& p, void* ws, const uint32_t* mask, hipStream_t s) {
+  if (mask) launch_partial_k<GT, true>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, s);
+  else launch_partial_k<GT, false>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, nullptr, s);
+}
+
+// eff[w] = live[w] & allow[w] for the words that hold rows [0, n), bits >= n cleared, zeros up to the end
+// of the last 64-column tile.  live / allow NULL = all ones; both are read in their first ceil(n / 32)
+// words only.  allow may be eff itself (each thread reads and writes its own word).
+__global__ __launch_bounds__(256) void mask_eff_kernel(const uint32_t* live, const uint32_t* allow, uint32_t* eff,
+                                                       long n, long words) {
+  for (long w = (long)blockIdx.x * 256 + threadIdx.x; w < words; w += (long)gridDim.x * 256) {
+    uint32_t v = 0;
+    if (w * 32 < n) {
+      v = (live ? live[w] : ~0u) & (allow ? allow[w] : ~0u);
+      if (n - w * 32 < 32) v &= (1u << (n - w * 32)) - 1u;
+    }
+    eff[w] = v;
+  }
 }
 
 // ---- 16-bit gallery rows: f32 -> storage (round to nearest even) and back (exact) -------------------
@@ -515,6 +599,25 @@ __global__ __launch_bounds__(256) void gal_widen_kernel(const GT* __restrict__ i
     ((float4*)out)[i] = gal4(in + 4 * i);
 }
 
+// Row i of `in` (f32 [n][E]) to row ids[i] of the gallery, rounded as gal_round_kernel rounds (an f32
+// gallery takes the bits).  The ids are distinct and inside the gallery (checked by the caller).
+__device__ __forceinline__ void gal_store4(float* out, long i4, float4 v) { ((float4*)out)[i4] = v; }
+template <typename GT> __device__ __forceinline__ void gal_store4(GT* out, long i4, float4 v) {
+  uint2 o;
+  o.x = round16(v.x, (GT*)nullptr) | (round16(v.y, (GT*)nullptr) << 16);
+  o.y = round16(v.z, (GT*)nullptr) | (round16(v.w, (GT*)nullptr) << 16);
+  ((uint2*)out)[i4] = o;
+}
+
+template <typename GT>
+__global__ __launch_bounds__(256) void gal_scatter_kernel(const float* __restrict__ in, const int64_t* __restrict__ ids,
+                                                          GT* __restrict__ gal, long n, int E4) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n * E4; i += (long)gridDim.x * 256) {
+    const long row = i / E4, c = i - row * E4;
+    gal_store4(gal, ids[row] * E4 + c, ((const float4*)in)[i]);
+  }
+}
+
 int convert_blocks(long n4) { return (int)std::min<long>((n4 + 255) / 256, 8192); }
 
 }  // namespace
@@ -541,6 +644,29 @@ hipError_t launch_gal_widen(int dtype, const void* in, float* out, long n, hipSt
   return hipGetLastError();
 }
 
+hipError_t launch_gal_scatter(int dtype, const float* in, const int64_t* ids, void* gal, long n, int E, hipStream_t s) {
+  if (n <= 0 || E <= 0 || E % 4) return hipErrorInvalidValue;
+  const int blocks = convert_blocks(n * (E / 4));
+  if (dtype == TOPK_GAL_F32)
+    hipLaunchKernelGGL(gal_scatter_kernel<float>, dim3(blocks), dim3(256), 0, s, in, ids, (float*)gal, n, E / 4);
+  else if (dtype == TOPK_GAL_F16)
+    hipLaunchKernelGGL(gal_scatter_kernel<_Float16>, dim3(blocks), dim3(256), 0, s, in, ids, (_Float16*)gal, n, E / 4);
+  else if (dtype == TOPK_GAL_BF16)
+    hipLaunchKernelGGL(gal_scatter_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, in, ids, (__bf16*)gal, n, E / 4);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+long topk_mask_words(long n) { return (n + 63) / 64 * 2; }
+
+hipError_t launch_topk_mask(const uint32_t* live, const uint32_t* allow, uint32_t* eff, long n, hipStream_t s) {
+  if (n <= 0 || !eff) return hipErrorInvalidValue;
+  const long words = topk_mask_words(n);
+  hipLaunchKernelGGL(mask_eff_kernel, dim3((int)std::min<long>((words + 255) / 256, 1024)), dim3(256), 0, s, live, allow,
+                     eff, n, words);
+  return hipGetLastError();
+}
+
 bool topk_narrow_route(int nq) {
   const int route = g_topk_route.load();
   if (route == 1 || nq > NB) return false;
@@ -562,15 +688,17 @@ TopkPlan topk_plan(long N, int nq, int max_blocks) {
 }
 
 hipError_t launch_topk(const float* q, int nq, const void* g, int dtype, int N, int E, float scale, float bias, int k,
-                       const TopkPlan& p, void* ws, int64_t* out_idx, float* out_score, hipStream_t s) {
+                       const TopkPlan& p, void* ws, const uint32_t* mask, int64_t* out_idx, float* out_score,
+                       hipStream_t s) {
   if (nq <= 0 || N <= 0 || E <= 0 || E % 16 != 0 || k < 1 || k > kTopkMax) return hipErrorInvalidValue;
   if (p.span_cols <= 0 || p.span_cols % TB != 0 || (long)p.n_spans * p.span_cols < N ||
       (long)(p.n_spans - 1) * p.span_cols >= N || (long)p.n_spans * k > INT32_MAX || p.n_spans > 65535)
     return hipErrorInvalidValue;
   if (p.narrow && nq > NB) return hipErrorInvalidValue;
-  if (dtype == TOPK_GAL_F32) launch_partial_k<float>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, s);
-  else if (dtype == TOPK_GAL_F16) launch_partial_k<_Float16>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, s);
-  else if (dtype == TOPK_GAL_BF16) launch_partial_k<__bf16>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, s);
+  if (mask && ((uintptr_t)mask & 7)) return hipErrorInvalidValue;
+  if (dtype == TOPK_GAL_F32) launch_partial_m<float>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, s);
+  else if (dtype == TOPK_GAL_F16) launch_partial_m<_Float16>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, s);
+  else if (dtype == TOPK_GAL_BF16) launch_partial_m<__bf16>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, s);
   else return hipErrorInvalidValue;
   hipLaunchKernelGGL(topk_merge_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, (const uint2*)ws, nq, p.n_spans, k,
                      out_idx, out_score);

@@ -7,8 +7,8 @@ runs in ``lib/libclipgpu.so`` (hand-written gfx950 HIP kernels + C++ host runtim
 from .clip import Clip
 from .config import ModelConfig, OpenClipConfig
 from .error import ClipError
-from .index import EmbeddingIndex
+from .index import EmbeddingIndex, pack_allow
 from .text import TextEmbedder
 from .vision import VisionEmbedder
 
-__all__ = ["Clip", "ClipError", "EmbeddingIndex", "TextEmbedder", "VisionEmbedder", "ModelConfig", "OpenClipConfig"]
+__all__ = ["Clip", "ClipError", "EmbeddingIndex", "pack_allow", "TextEmbedder", "VisionEmbedder", "ModelConfig", "OpenClipConfig"]

@@ -67,6 +67,14 @@ _PROTOS = [
     ("clipgpu_index_search", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_void_p, c_void_p]),
     ("clipgpu_index_search_device", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_void_p, c_void_p,
                                             c_void_p]),
+    ("clipgpu_index_remove", c_int, [c_void_p, c_void_p, c_int64]),
+    ("clipgpu_index_live", c_int64, [c_void_p]),
+    ("clipgpu_index_get_live", c_int, [c_void_p, c_int64, c_int64, c_void_p]),
+    ("clipgpu_index_set_rows", c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
+    ("clipgpu_index_search_filtered", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_void_p,
+                                              c_void_p, c_void_p]),
+    ("clipgpu_index_search_filtered_device", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_void_p,
+                                                     c_void_p, c_void_p, c_void_p]),
     ("clipgpu_comm_unique_id", c_int, [c_void_p]),
     ("clipgpu_comm_init_rank", c_int, [c_void_p, c_void_p, c_int, c_int]),
     ("clipgpu_comm_info", c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),

@@ -133,14 +133,16 @@ class Clip:
         index.add(embs)
         return index
 
-    def search(self, index, texts: Sequence[str], k: int) -> List[List[Tuple[int, float]]]:
+    def search(self, index, texts: Sequence[str], k: int, allow=None) -> List[List[Tuple[int, float]]]:
         """Semantic search (examples/search.rs; rank_images, src/clip.rs:134-170, cut to its k best):
         per text the k best rows of ``index`` as (gallery index, logit), best first, equal logits by
         ascending index.  The logits use the model's logit_scale / logit_bias (defaults 1.0 / 0.0).
         Logits, not probabilities: a softmax over the gallery needs every score of the row and
-        stays with ``rank_images_many``."""
+        stays with ``rank_images_many``.  Removed rows never appear; ``allow`` (a bool array
+        [len(index)]) restricts the search to the rows where it is True, and a text gets fewer than k
+        pairs when fewer rows are allowed."""
         scale, bias = self._scale_bias()
-        idx, score = index.search(self.text.embed_texts(texts), k, float(scale), float(bias))
+        idx, score = index.search(self.text.embed_texts(texts), k, float(scale), float(bias), allow=allow)
         return [[(int(i), float(s)) for i, s in zip(ri, rs) if i >= 0] for ri, rs in zip(idx, score)]
 
     @staticmethod

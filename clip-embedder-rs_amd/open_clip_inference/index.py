@@ -16,6 +16,19 @@ TOPK_MAX = 128  # CLIPGPU_TOPK_MAX
 DTYPES = {"f32": 0, "f16": 1, "bf16": 2}  # enum clipgpu_index_dtype
 
 
+def pack_allow(allowed) -> np.ndarray:
+    """A bool array [n] as the ``allow`` bitmap of ``clipgpu_index_search_filtered``: ceil(n / 32)
+    ``np.uint32`` words, row i at bit ``i & 31`` of word ``i >> 5``, zero-padded -- the words that
+    ``np.packbits(allowed, bitorder="little")`` gives when read as little-endian ``uint32``."""
+    a = np.asarray(allowed)
+    if a.dtype != np.bool_ or a.ndim != 1:
+        raise TypeError(f"allow must be a 1-d bool array, got dtype {a.dtype} with {a.ndim} dimensions")
+    words = (a.size + 31) // 32
+    bits = np.zeros(words * 32, np.uint64)
+    bits[:a.size] = a
+    return (bits.reshape(words, 32) << np.arange(32, dtype=np.uint64)).sum(axis=1, dtype=np.uint64).astype(np.uint32)
+
+
 class EmbeddingIndex:
     """``E``-dimensional rows (E % 16 == 0), at most ``capacity`` of them (fixed: the device
     memory is allocated here), on GPU ``device``.  Rows keep the order they were added in; a search
@@ -24,7 +37,9 @@ class EmbeddingIndex:
     a million 512-d rows, and no faster from 16 queries on: its kernels are not bound by reading the
     gallery).  Rows are always given as f32; a 16-bit
     index rounds them to nearest even on the device, and a search returns exactly what an f32 index
-    of the rounded rows returns (include/clipgpu.h has the bound on a logit's change)."""
+    of the rounded rows returns (include/clipgpu.h has the bound on a logit's change).  ``remove``
+    marks rows dead without moving the others, ``set_rows`` overwrites rows in place (and revives
+    them), and ``search(..., allow=)`` searches a subset, exactly."""
 
     def __init__(self, E: int, capacity: int, device: int = 0, dtype: str = "f32"):
         self._h = None
@@ -76,6 +91,43 @@ class EmbeddingIndex:
             raise ShapeError(f"Shape error: {what} must be [n, {self.E}], got {x.shape}")
         return x
 
+    def _ids(self, ids) -> np.ndarray:
+        x = np.atleast_1d(np.asarray(ids))
+        if x.ndim != 1 or (x.size and not np.issubdtype(x.dtype, np.integer)):
+            raise TypeError("ids must be a 1-d array of integers")
+        return np.ascontiguousarray(x, dtype=np.int64)
+
+    def remove(self, ids) -> None:
+        """Marks the rows at ``ids`` dead: they never appear in a result again; all other rows keep
+        their positions and ``len(self)`` is unchanged (it counts slots; ``live`` counts rows).
+        Removing a dead row is a no-op and ids may repeat; an id outside [0, len(self)) raises and
+        changes nothing."""
+        x = self._ids(ids)
+        check(lib().clipgpu_index_remove(self.handle, x.ctypes.data, x.size))
+
+    @property
+    def live(self) -> int:
+        """The number of live rows."""
+        return int(lib().clipgpu_index_live(self.handle))
+
+    def is_live(self) -> np.ndarray:
+        """A bool array [len(self)]: True where the row is live."""
+        out = np.empty(len(self), np.uint8)
+        if out.size:
+            check(lib().clipgpu_index_get_live(self.handle, 0, out.size, out.ctypes.data))
+        return out.astype(bool)
+
+    def set_rows(self, ids, rows) -> None:
+        """Overwrites the rows at ``ids`` (each < len(self), none twice) with ``rows`` [n, E] and marks
+        them live: how the slot of a removed row is used again.  A 16-bit index rounds the rows as
+        ``add`` does.  A bad or repeated id raises and changes nothing."""
+        x = self._ids(ids)
+        r = self._rows(rows, "rows")
+        if r.shape[0] != x.size:
+            from .error import ShapeError
+            raise ShapeError(f"Shape error: {x.size} ids for {r.shape[0]} rows")
+        check(lib().clipgpu_index_set_rows(self.handle, x.ctypes.data, r.ctypes.data, x.size))
+
     def add(self, rows) -> None:
         """Appends host rows [n, E]; raises "index full" (and adds nothing) beyond the capacity."""
         x = self._rows(rows, "rows")
@@ -95,23 +147,37 @@ class EmbeddingIndex:
         index reads the rows four at a time: ``d_rows`` must then be 16-byte aligned."""
         check(lib().clipgpu_index_add_device(self.handle, c_void_p(d_rows), int(n), c_void_p(stream or None)))
 
-    def search(self, queries, k: int, logit_scale: float = 1.0, logit_bias: float = 0.0
+    def search(self, queries, k: int, logit_scale: float = 1.0, logit_bias: float = 0.0, allow=None
                ) -> Tuple[np.ndarray, np.ndarray]:
         """The k best rows per query, best first: (indices int64 [nq, k], scores f32 [nq, k]) with
         score = dot(query, row).mul_add(logit_scale, logit_bias), bit-identical to
-        ``similarity(..., "logits")``; equal scores come out by ascending index.  Slots beyond
-        min(k, len(self)) hold (-1, -inf).  1 <= k <= 128."""
+        ``similarity(..., "logits")``; equal scores come out by ascending index.  Removed rows never
+        appear; ``allow`` (a bool array [len(self)], one for all queries) restricts the search to the
+        rows where it is True, exactly: the result is that of an index holding only those rows.  Slots
+        beyond min(k, live allowed rows) hold (-1, -inf).  1 <= k <= 128."""
+        words = None
+        if allow is not None:
+            a = np.asarray(allow)
+            if a.dtype != np.bool_ or a.ndim != 1:
+                raise TypeError(f"allow must be a 1-d bool array, got dtype {a.dtype} with {a.ndim} dimensions")
+            if a.size != len(self):
+                from .error import ShapeError
+                raise ShapeError(f"Shape error: allow must have len(index) = {len(self)} entries, got {a.size}")
+            words = pack_allow(a)
         q = self._rows(queries, "queries")
         idx = np.empty((q.shape[0], int(k)), np.int64)
         score = np.empty((q.shape[0], int(k)), np.float32)
-        check(lib().clipgpu_index_search(self.handle, q.ctypes.data, q.shape[0], int(k), float(logit_scale),
-                                         float(logit_bias), idx.ctypes.data, score.ctypes.data))
+        check(lib().clipgpu_index_search_filtered(self.handle, q.ctypes.data, q.shape[0], int(k), float(logit_scale),
+                                                  float(logit_bias), None if words is None else words.ctypes.data,
+                                                  idx.ctypes.data, score.ctypes.data))
         return idx, score
 
     def search_device(self, d_queries: int, nq: int, k: int, d_idx: int, d_score: int, logit_scale: float = 1.0,
-                      logit_bias: float = 0.0, stream: int = 0) -> None:
+                      logit_bias: float = 0.0, stream: int = 0, d_allow: int = 0) -> None:
         """``search`` on device pointers (queries f32 [nq, E] in; int64 [nq, k] and f32 [nq, k] out),
-        ordered on ``stream``; returns without synchronising."""
-        check(lib().clipgpu_index_search_device(self.handle, c_void_p(d_queries), int(nq), int(k), float(logit_scale),
-                                                float(logit_bias), c_void_p(d_idx), c_void_p(d_score),
-                                                c_void_p(stream or None)))
+        ordered on ``stream``; returns without synchronising.  ``d_allow``: a device pointer to the
+        ``pack_allow`` words of an allow array (0 = none); it is read on ``stream``."""
+        check(lib().clipgpu_index_search_filtered_device(self.handle, c_void_p(d_queries), int(nq), int(k),
+                                                         float(logit_scale), float(logit_bias),
+                                                         c_void_p(d_allow or None), c_void_p(d_idx), c_void_p(d_score),
+                                                         c_void_p(stream or None)))

@@ -309,7 +309,32 @@ int clipgpu_similarity_device(const float* d_img, int64_t n_img, const float* d_
  *
  * Few queries: a launch of at most 16 query rows (the last chunk of any call included) may run a
  * few-query kernel instead of the 64-row-tile one.  The results are bit-identical; the route shows
- * only in the time (embedding index, has the measured threshold). */
+ * only in the time (embedding index, has the measured threshold).
+ *
+ * Removal, replacement and filters.  clipgpu_index_remove marks the rows at `ids` (host, n of them) dead:
+ * a dead row never appears in a result, every other row keeps its position (a caller's ids are stable)
+ * and clipgpu_index_size is unchanged -- it counts slots; clipgpu_index_live counts the live rows.
+ * Removing a dead row is a no-op and ids may repeat; an id outside [0, size) is CLIPGPU_ERR_INVALID and
+ * nothing changes.  clipgpu_index_get_live writes one byte per row of [first, first + n), 1 = live (the
+ * range rules of clipgpu_index_get_rows).  clipgpu_index_set_rows overwrites the rows at `ids` with host
+ * f32 rows [n][E] (a 16-bit index rounds them exactly as add does) and marks them live: the way to reuse
+ * the slot of a removed row instead of running out of capacity.  Every id must be < size and none may
+ * repeat, else CLIPGPU_ERR_INVALID and nothing changes.  add / add_device append live rows as before;
+ * clipgpu_index_clear makes every future row live again.  remove, get_live and set_rows synchronise.
+ *   clipgpu_index_search_filtered[_device] search the rows that are live AND allowed.  `allow` is a
+ * bitmap of uint32 words: row i is allowed iff bit (i & 31) of word (i >> 5) is set -- numpy's
+ * packbits(bitorder="little") read as little-endian words.  It is read in its first ceil(size / 32)
+ * words only, bits at and past `size` in the last word are ignored, it needs 4-byte alignment, one
+ * bitmap serves all queries of the call, and NULL means live rows only.  The host form takes a host
+ * bitmap, the _device form a device bitmap on `device` (read on `stream`; it must stay valid and
+ * unchanged until the search has run).  The filter is exact: the result is, bit for bit, the unfiltered
+ * search of an index that holds only the allowed live rows, with its indices mapped back; a row that is
+ * not allowed never enters a list (a NaN score does: it ranks below -inf).  Slots beyond
+ * min(k, allowed live rows) hold (-1, -inf); an index whose rows are all removed or filtered out returns
+ * only such slots and no error; size == 0 stays "Empty batch".  clipgpu_index_search[_device] are the
+ * filtered forms with allow = NULL: they honour removals, and on an index without removed rows they
+ * run the kernels they always ran.  The two bitmaps a search needs (live rows; live AND allow) are part
+ * of the work area allocated at creation (capacity / 4 bytes together): a search still allocates nothing. */
 typedef struct clipgpu_index clipgpu_index;
 #define CLIPGPU_TOPK_MAX 128
 enum clipgpu_index_dtype { CLIPGPU_INDEX_F32 = 0, CLIPGPU_INDEX_F16 = 1, CLIPGPU_INDEX_BF16 = 2 };
@@ -326,6 +351,15 @@ int clipgpu_index_search(clipgpu_index* ix, const float* queries, int64_t nq, in
                          float logit_bias, int64_t* out_idx, float* out_score);
 int clipgpu_index_search_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k, float logit_scale,
                                 float logit_bias, int64_t* d_idx, float* d_score, void* stream);
+int clipgpu_index_remove(clipgpu_index* ix, const int64_t* ids, int64_t n); /* host ids */
+int64_t clipgpu_index_live(const clipgpu_index* ix);                         /* live rows, exactly */
+int clipgpu_index_get_live(clipgpu_index* ix, int64_t first, int64_t n, uint8_t* out); /* host [n], 0 / 1 */
+int clipgpu_index_set_rows(clipgpu_index* ix, const int64_t* ids, const float* rows, int64_t n); /* host */
+int clipgpu_index_search_filtered(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, float logit_scale,
+                                  float logit_bias, const uint32_t* allow, int64_t* out_idx, float* out_score);
+int clipgpu_index_search_filtered_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k,
+                                         float logit_scale, float logit_bias, const uint32_t* d_allow, int64_t* d_idx,
+                                         float* d_score, void* stream);
 
 /* ---- data-parallel sharding + the RCCL all-gather (north_star: "batches shard
  * data-parallel across the 8 GPUs of one node with an RCCL all-gather over xGMI only for the final

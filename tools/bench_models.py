@@ -296,6 +296,75 @@ def topk_routes_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 2, 4, 8, 12
         ix.close()
 
 
+def topk_filter_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 16, 256)):
+    """What an allow bitmap costs and saves (clipgpu_index_search_filtered_device, f32 gallery): six legs
+    alternate in one process, their order rotating from round to round -- the unfiltered search, and the
+    filtered search under a bitmap of all ones (the overhead of the mask), a random 50 % and a random 1 %
+    of the rows (no 64-column tile is empty: nothing to skip), and one contiguous range of 10 % of the rows
+    (whole spans are empty), and the same result by the full-matrix path (clipgpu_similarity_device logits,
+    masked_fill(-inf), torch.topk; timed under the 50 % bitmap).  Per leg the median and the spread of
+    `runs` device-event timings after `warmup` rounds.  Every fused leg returns the indices and the
+    bit-equal scores of the full-matrix path under its bitmap (computed once more, untimed, per bitmap)."""
+    import ctypes
+    from open_clip_inference import EmbeddingIndex
+    from open_clip_inference.index import pack_allow
+    torch.manual_seed(0)
+    rng = np.random.default_rng(0)
+    L = _lib.lib()
+    s = torch.cuda.current_stream().cuda_stream
+    g = torch.nn.functional.normalize(torch.randn(N, E, device="cuda"), dim=1)
+    allows = {"all_ones": np.ones(N, bool), "random_50pct": rng.random(N) < 0.5, "random_1pct": rng.random(N) < 0.01,
+              "range_10pct": (np.arange(N) >= N // 3) & (np.arange(N) < N // 3 + N // 10)}
+    d_bool = {name: torch.from_numpy(a).cuda() for name, a in allows.items()}
+    d_words = {name: torch.from_numpy(pack_allow(a).view(np.int32)).cuda() for name, a in allows.items()}
+    ix = EmbeddingIndex(E, N)
+    ix.add_device(g.data_ptr(), N, s)
+    try:
+        for Q in Qs:
+            q = torch.nn.functional.normalize(torch.randn(Q, E, device="cuda"), dim=1)
+            mat = torch.empty(Q, N, device="cuda")
+            names = ["unfiltered"] + list(allows)
+            res = {name: (torch.empty((Q, k), dtype=torch.int64, device="cuda"), torch.empty((Q, k), device="cuda"))
+                   for name in names}
+
+            def fused(name):
+                ix.search_device(q.data_ptr(), Q, k, res[name][0].data_ptr(), res[name][1].data_ptr(), 100.0, 0.0, s,
+                                 d_allow=0 if name == "unfiltered" else d_words[name].data_ptr())
+
+            def baseline(name="random_50pct"):
+                _lib.check(L.clipgpu_similarity_device(ctypes.c_void_p(q.data_ptr()), Q, ctypes.c_void_p(g.data_ptr()),
+                                                       N, E, 100.0, 0.0, 2, 1, ctypes.c_void_p(mat.data_ptr()),
+                                                       ctypes.c_void_p(s)))
+                if name != "unfiltered":
+                    mat.masked_fill_(~d_bool[name][None, :], float("-inf"))
+                return torch.topk(mat, k, dim=1)
+
+            legs = tuple((name, (lambda n=name: fused(n))) for name in names) + (("baseline", baseline),)
+            ms = {name: [] for name, _ in legs}
+            for rnd in range(warmup + runs):
+                r = rnd % len(legs)
+                for name, fn in legs[r:] + legs[:r]:  # every leg follows every other equally often
+                    t = _event_ms(fn)
+                    if rnd >= warmup:
+                        ms[name].append(t)
+            for name in names:  # the same result: scores bit for bit; indices once the baseline's ties are in index order
+                b_score, b_idx = (x.cpu().numpy() for x in baseline(name))
+                order = np.lexsort((b_idx, -b_score.astype(np.float64)), axis=1)
+                b_idx, b_score = np.take_along_axis(b_idx, order, 1), np.take_along_axis(b_score, order, 1)
+                assert np.array_equal(res[name][1].cpu().numpy().view(np.uint32), b_score.view(np.uint32)), name
+                assert np.array_equal(res[name][0].cpu().numpy(), b_idx), name
+            nbytes = N * E * 4
+            out = {"measure": "topk_filter", "Q": Q, "N": N, "E": E, "k": k, "runs": runs, "same_as_baseline": True,
+                   "allowed_rows": {name: int(a.sum()) for name, a in allows.items()}}
+            for name, v in ms.items():
+                out[name] = _stats(v, nbytes)
+            for name in allows:
+                out[name + "_over_unfiltered"] = round(out[name]["ms_median"] / out["unfiltered"]["ms_median"], 3)
+            print(json.dumps(out), flush=True)
+    finally:
+        ix.close()
+
+
 def latency_leg(steps=50, warmup=10):
     """Single-item latency (the reference's embed_image / embed_text calls, B = 1) through the
     host entry points: pinned staging + H2D + forward + D2H + synchronise, ViT-B/32."""
@@ -343,6 +412,8 @@ if __name__ == "__main__":
         topk_leg()
     if "topkroutes" in which:  # the few-query kernel vs the wide one per query count: sets kNarrowRows
         topk_routes_leg()
+    if "topkfilter" in which:  # the filtered search: the cost of the mask and the gain from the skips
+        topk_filter_leg()
     if "so400m" in which:
         device_leg("so400m_vision", SO400M_16_SIGLIP2_384_CFG, 0, 128)
     if "h14" in which:
