@@ -13,6 +13,11 @@
 // = every row live) and mirrored to the work area.  A search with removed rows or an allow bitmap first
 // writes eff = live & allow into the work area (once per call) and runs the masked kernels on it; any
 // other search runs the unmasked kernels as before.
+//
+// Probabilities (clipgpu_index_search_probs).  The same search with one more output, the softmax over the
+// searched rows or the sigmoid of the k results.  The softmax needs one (max, sum) pair per (query row,
+// span); they live in the work area too (64 pairs per phase-1 block the workspace holds), as do the host
+// form's staged probabilities and (max, sum) rows.  The other searches run the kernels they ran before.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,13 +48,16 @@ struct clipgpu_index {
   int dtype = CLIPGPU_INDEX_F32;  // the gallery's element type
   int64_t esz = 4;                // its bytes
   char* gallery = nullptr;        // [capacity][E] of esz bytes
-  char* work = nullptr;      // ws | staged queries | staged indices | staged scores | live | eff
+  char* work = nullptr;      // ws | staged queries | staged indices | staged scores | live | eff | pairs | staged probs | staged norms
   int ws_blocks = 0;         // phase-1 blocks the workspace holds: min(kMaxBlocks, 4 * 64-row tiles of capacity)
   float* st_q = nullptr;
   int64_t* st_idx = nullptr;
   float* st_score = nullptr;
   uint32_t* d_live = nullptr;    // the mirror of h_live; bits at and past `size` are ones; read only while n_dead > 0
   uint32_t* d_eff = nullptr;     // the filter of the search in flight: live & allow, whole 64-row tiles
+  void* d_ms = nullptr;          // the softmax search in flight: one (max, sum) per (query row, span), 64 * ws_blocks
+  float* st_prob = nullptr;
+  float* st_norm = nullptr;
   std::vector<uint32_t> h_live;  // bit i: row i is live; ceil(capacity / 32) words, empty = every row live
   int64_t n_dead = 0;            // cleared bits of h_live below `size`
   float* scratch = nullptr;      // 16-bit index: f32 rows on their way in (add) or out (get_rows); lazy
@@ -89,16 +97,31 @@ const uint32_t* build_mask(clipgpu_index* ix, const uint32_t* d_allow, hipStream
   return ix->d_eff;
 }
 
-// Searches d_q [nq][E] in chunks of kQueryChunk rows on `s`, all under one mask.
+// Searches d_q [nq][E] in chunks of kQueryChunk rows on `s`, all under one mask.  probs: TOPK_PROBS_NONE, or
+// the probabilities too (d_prob [nq][k]; d_norm [nq][2] or NULL, softmax only).  The span cut is the same with
+// and without them: a launch of B phase-1 blocks writes at most 64 B pairs (wide: 64 rows per block; few-query:
+// 16 rows and at most 4 * ws_blocks spans), which the pair area holds.
 void search_on(clipgpu_index* ix, const float* d_q, int64_t nq, int64_t k, float scale, float bias,
-               const uint32_t* mask, int64_t* d_idx, float* d_score, hipStream_t s) {
+               const uint32_t* mask, int64_t* d_idx, float* d_score, hipStream_t s, int probs = TOPK_PROBS_NONE,
+               float* d_prob = nullptr, float* d_norm = nullptr) {
   for (int64_t q0 = 0; q0 < nq; q0 += kQueryChunk) {
     const int rows = (int)std::min(kQueryChunk, nq - q0);
     const TopkPlan p = topk_plan(ix->size, rows, ix->ws_blocks);  // the route too: few rows, few-query kernel
+    const TopkProbs pr = {probs, ix->d_ms, 64L * ix->ws_blocks, d_prob ? d_prob + q0 * k : nullptr,
+                          d_norm ? d_norm + q0 * 2 : nullptr};
     HIP_CHECK(launch_topk(d_q + q0 * ix->E, rows, ix->gallery, ix->dtype, (int)ix->size, (int)ix->E, scale, bias,
-                         (int)k, p, ix->work, mask, d_idx + q0 * k, d_score + q0 * k, s));
+                         (int)k, p, ix->work, mask, d_idx + q0 * k, d_score + q0 * k, s,
+                         probs == TOPK_PROBS_NONE ? nullptr : &pr));
   }
   mark_last(ix, s);
+}
+
+// The activation of a probability search as the kernels name it; refused before any device call.
+int probs_kind(int activation) {
+  if (activation == CLIPGPU_SIM_SOFTMAX) return TOPK_PROBS_SOFTMAX;
+  if (activation == CLIPGPU_SIM_SIGMOID) return TOPK_PROBS_SIGMOID;
+  throw ClipErr(CLIPGPU_ERR_INVALID, "activation must be CLIPGPU_SIM_SOFTMAX or CLIPGPU_SIM_SIGMOID "
+                                     "(logits: clipgpu_index_search_filtered)");
 }
 
 // The live words that hold rows [0, size) to the device mirror (synchronous).  Callers hold the mutex
@@ -163,8 +186,9 @@ int clipgpu_index_create_ex(int device, int64_t E, int64_t capacity, int dtype, 
     const size_t sq = align256((size_t)kQueryChunk * E * 4), si = align256((size_t)kQueryChunk * kTopkMax * 8);
     const size_t ss = align256((size_t)kQueryChunk * kTopkMax * 4);
     const size_t sl = align256((size_t)live_words(capacity) * 4), se = align256((size_t)topk_mask_words(capacity) * 4);
+    const size_t sm = align256((size_t)ix->ws_blocks * 64 * 8), sn = align256((size_t)kQueryChunk * 2 * 4);
     hipError_t err = hipMalloc((void**)&ix->gallery, (size_t)capacity * E * ix->esz);
-    if (err == hipSuccess) err = hipMalloc((void**)&ix->work, ws + sq + si + ss + sl + se);
+    if (err == hipSuccess) err = hipMalloc((void**)&ix->work, ws + sq + si + ss + sl + se + sm + ss + sn);
     if (err == hipSuccess) err = hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking);
     if (err == hipSuccess) err = hipEventCreateWithFlags(&ix->done, hipEventDisableTiming);
     if (err != hipSuccess) {
@@ -176,6 +200,9 @@ int clipgpu_index_create_ex(int device, int64_t E, int64_t capacity, int dtype, 
     ix->st_score = (float*)(ix->work + ws + sq + si);
     ix->d_live = (uint32_t*)(ix->work + ws + sq + si + ss);
     ix->d_eff = (uint32_t*)(ix->work + ws + sq + si + ss + sl);
+    ix->d_ms = ix->work + ws + sq + si + ss + sl + se;
+    ix->st_prob = (float*)(ix->work + ws + sq + si + ss + sl + se + sm);
+    ix->st_norm = (float*)(ix->work + ws + sq + si + ss + sl + se + sm + ss);
     *out = ix;
   });
 }
@@ -400,6 +427,52 @@ int clipgpu_index_search_filtered(clipgpu_index* ix, const float* queries, int64
       HIP_CHECK(hipStreamSynchronize(ix->stream));
       HIP_CHECK(copy_d2h(out_idx + q0 * k, ix->st_idx, (size_t)rows * k * 8));
       HIP_CHECK(copy_d2h(out_score + q0 * k, ix->st_score, (size_t)rows * k * 4));
+    }
+  });
+}
+
+int clipgpu_index_search_probs_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k,
+                                      float logit_scale, float logit_bias, int activation, const uint32_t* d_allow,
+                                      int64_t* d_idx, float* d_score, float* d_prob, float* d_norm, void* stream) {
+  return guarded([&]() {
+    const int probs = probs_kind(activation);
+    check_search(ix, d_queries, nq, k, d_idx, d_score);
+    if (!d_prob) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (ix->size == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
+    HIP_CHECK(hipSetDevice(ix->device));
+    hipStream_t s = (hipStream_t)stream;
+    order_after_last(ix, s);
+    const uint32_t* mask = build_mask(ix, d_allow, s);
+    search_on(ix, d_queries, nq, k, logit_scale, logit_bias, mask, d_idx, d_score, s, probs, d_prob,
+              probs == TOPK_PROBS_SOFTMAX ? d_norm : nullptr);
+  });
+}
+
+int clipgpu_index_search_probs(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, float logit_scale,
+                               float logit_bias, int activation, const uint32_t* allow, int64_t* out_idx,
+                               float* out_score, float* out_prob, float* out_norm) {
+  return guarded([&]() {
+    const int probs = probs_kind(activation);
+    check_search(ix, queries, nq, k, out_idx, out_score);
+    if (!out_prob) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (ix->size == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
+    HIP_CHECK(hipSetDevice(ix->device));
+    HIP_CHECK(hipEventSynchronize(ix->done));  // the staging buffers and the filter area are free
+    if (allow) HIP_CHECK(copy_h2d(ix->d_eff, allow, (size_t)live_words(ix->size) * 4));
+    const uint32_t* mask = build_mask(ix, allow ? ix->d_eff : nullptr, ix->stream);
+    const bool norm = out_norm && probs == TOPK_PROBS_SOFTMAX;
+    for (int64_t q0 = 0; q0 < nq; q0 += kQueryChunk) {
+      const int64_t rows = std::min(kQueryChunk, nq - q0);
+      HIP_CHECK(copy_h2d(ix->st_q, queries + q0 * ix->E, (size_t)rows * ix->E * 4));
+      search_on(ix, ix->st_q, rows, k, logit_scale, logit_bias, mask, ix->st_idx, ix->st_score, ix->stream, probs,
+                ix->st_prob, norm ? ix->st_norm : nullptr);
+      HIP_CHECK(hipStreamSynchronize(ix->stream));
+      HIP_CHECK(copy_d2h(out_idx + q0 * k, ix->st_idx, (size_t)rows * k * 8));
+      HIP_CHECK(copy_d2h(out_score + q0 * k, ix->st_score, (size_t)rows * k * 4));
+      HIP_CHECK(copy_d2h(out_prob + q0 * k, ix->st_prob, (size_t)rows * k * 4));
+      if (norm) HIP_CHECK(copy_d2h(out_norm + q0 * 2, ix->st_norm, (size_t)rows * 2 * 4));
     }
   });
 }

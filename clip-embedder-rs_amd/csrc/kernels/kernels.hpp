@@ -216,9 +216,17 @@ extern std::atomic<int> g_topk_route;
 TopkPlan topk_plan(long N, int nq, int max_blocks);
 // mask: NULL (every row, the unmasked kernels) or the filter bitmap of launch_topk_mask (the MASKED
 // kernels): only rows whose bit is set enter a result, out slots beyond min(k, allowed rows) are (-1, -inf).
+// pr: NULL (logits only, the kernels as they were) or the probabilities of the k results, out_prob [nq][k]
+// (0 in the empty slots).  TOPK_PROBS_SOFTMAX: exp(l - M) / S over every row the search counts (in range,
+// allowed), M their largest logit and S = sum exp(l - M), from one (m, s) pair per (query row, span) that
+// the PROBS phase-1 kernels write to ms (8-byte aligned, room for ms_pairs >= nq * n_spans pairs); (M, S)
+// goes to out_norm [nq][2] if given.  TOPK_PROBS_SIGMOID: 1 / (1 + expf(-l)), similarity.hip's expression,
+// in the merge alone (ms, out_norm unused).  DESIGN.md (embedding index) derives the error bound.
+enum TopkProbsKind { TOPK_PROBS_NONE = 0, TOPK_PROBS_SOFTMAX = 1, TOPK_PROBS_SIGMOID = 2 };
+struct TopkProbs { int activation; void* ms; long ms_pairs; float* out_prob; float* out_norm; };
 hipError_t launch_topk(const float* q, int nq, const void* g, int dtype, int N, int E, float scale, float bias, int k,
                        const TopkPlan& p, void* ws, const uint32_t* mask, int64_t* out_idx, float* out_score,
-                       hipStream_t s);
+                       hipStream_t s, const TopkProbs* pr = nullptr);
 // The filter bitmap the MASKED kernels read: row i is allowed iff bit i & 31 of word i >> 5 is set.
 // eff (8-byte aligned, topk_mask_words(n) words: whole 64-column tiles) = live & allow over rows [0, n),
 // bits >= n cleared.  live / allow: device words, NULL = all ones, read in their first ceil(n / 32) words;

@@ -30,6 +30,13 @@
 // column whose bit is clear does not pass the ballot, so it never enters a list -- unlike a NaN score,
 // which ranks below -inf but is an entry.  A span with no allowed row hands the merge k empty entries.
 // The MASKED = false instantiations are the kernels as they were: an unfiltered search launches them.
+//
+// Probabilities (PROBS instantiations of both phase-1 kernels and of the merge): the softmax over every row
+// the search counts needs only a running (max, sum exp(l - max)) pair per query row, kept in registers where
+// the scores already are, written once per (row, span) and combined in the merge, which then also writes
+// exp(l - M) / S for the k results (or their sigmoid, which needs the merge alone).  ms_add / ms_group16
+// below; the error bound is derived in DESIGN.md (embedding index, probabilities).  The PROBS = false
+// instantiations are the kernels as they were.
 #include <algorithm>
 #include <atomic>
 #include <cstdint>
@@ -117,12 +124,35 @@ __device__ __forceinline__ uint64_t compact_row(uint2* ent, int k, int c, int la
   return ent_key(ent[k - 1]);
 }
 
+// ---- softmax normaliser (PROBS instantiations) -----------------------------------------------------
+// A row's running pair (m, s): m = the largest logit fed so far, s = sum exp(l - m) over them, by online
+// rescaling: a logit above m rescales s by expf(m - l) and counts itself as 1, any other adds expf(l - m).
+// Start: (-inf, 0).  A NaN logit makes s NaN for good (m ignores it); -inf adds nothing; +inf leaves
+// m = +inf, which the merge turns into a NaN sum, as exp(inf - inf) does in softmax_rows_kernel.
+__device__ __forceinline__ void ms_add(float& m, float& s, float l) {
+  const bool up = l > m;
+  const float a = expf(up ? m - l : l - m);  // one exp either way; unused for -inf against -inf (NaN)
+  if (up) {
+    s = s * a + 1.0f;
+    m = l;
+  } else if (l != -INFINITY) {
+    s += a;
+  }
+}
+// The pairs of the 16 lanes that share lane >> 4 (one accumulator row), as one pair: the maximum is exact,
+// every lane rescales its sum once (by exactly 1 where it holds the maximum), then a fixed add tree.
+__device__ __forceinline__ float2 ms_group16(float m, float s) {
+  const float M = group16_max(m);
+  return make_float2(M, group16_sum(m == M ? s : s * expf(m - M)));
+}
+
 // KC: list capacity the LDS is sized for (k <= KC); the LDS sets the blocks per CU (2 / 2 / 1 / 1 for
 // KC 16 / 32 / 64 / 128), which the register budget follows.  Block: 64 queries x one gallery span.
-template <int KC, typename GT, bool MASKED>
+// PROBS: every counted column's logit also feeds its row's (m, s); one pair per (row, span) goes to ms.
+template <int KC, typename GT, bool MASKED, bool PROBS>
 __global__ __launch_bounds__(256, KC <= 32 ? 2 : 1) void topk_partial_kernel(
     const float* __restrict__ qry, const GT* __restrict__ gal, int nq, int N, int E, float scale, float bias, int k,
-    int span_cols, int n_spans, uint2* __restrict__ ws, const uint2* __restrict__ mask) {
+    int span_cols, int n_spans, uint2* __restrict__ ws, const uint2* __restrict__ mask, float2* __restrict__ ms) {
   constexpr int STRIDE = KC + CAND1;
   __shared__ __attribute__((aligned(16))) float stage[2][TB * LDT];  // A | B: [row][k slot qd][k step]
   __shared__ uint2 sel[TB * STRIDE];
@@ -143,6 +173,8 @@ __global__ __launch_bounds__(256, KC <= 32 ? 2 : 1) void topk_partial_kernel(
         if (i0 + row < nq) {
           uint2* dst = ws + ((long)(i0 + row) * n_spans + span) * k;
           for (int t = lane; t < k; t += 64) dst[t] = ent_empty();
+          if constexpr (PROBS)
+            if (lane == 0) ms[(long)(i0 + row) * n_spans + span] = make_float2(-INFINITY, 0.f);
         }
       return;
     }
@@ -153,6 +185,7 @@ __global__ __launch_bounds__(256, KC <= 32 ? 2 : 1) void topk_partial_kernel(
   const int rowbase = wave * 16;
   const int r = lane & 15, qd = lane >> 4;
   uint64_t thr[4] = {0, 0, 0, 0};  // thresholds of rows rowbase + 4 * qd + e
+  float pm[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, ps[4] = {0.f, 0.f, 0.f, 0.f};  // PROBS: their (m, s)
   // Staging: a slab is 64 k = 16 MFMA steps.  Thread -> (rows tid / 16 + 16 p, p < 4; k step tid % 16):
   // one float4 = the four k slots of one step, 256 contiguous bytes per row across 16 threads.  In LDS
   // a row lies as [k slot qd][k step], so a lane's operands of four steps are one 16-byte read
@@ -226,6 +259,19 @@ __global__ __launch_bounds__(256, KC <= 32 ? 2 : 1) void topk_partial_kernel(
       }
     }
     // C[row = 4 * qd + e][col = r] of column tile t
+    if constexpr (PROBS) {
+      // The counted columns (in range, allowed) feed their rows' pairs, ascending, whatever the thresholds
+      // are; rows past nq keep pairs of their own that are never written.  A loop of its own: inside the
+      // selection's it made that loop too large to unroll, and thr / pm / ps left the registers.
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          bool ok = j0 + t * 16 + r < c_end;
+          if constexpr (MASKED) ok = ok && (((t < 2 ? mw.x : mw.y) >> ((t & 1) * 16 + r)) & 1u) != 0;
+          if (ok) ms_add(pm[e], ps[e], fmaf(acc[t][e], scale, bias));
+        }
+    }
 #pragma unroll
     for (int e = 0; e < 4; ++e)
 #pragma unroll
@@ -272,11 +318,26 @@ __global__ __launch_bounds__(256, KC <= 32 ? 2 : 1) void topk_partial_kernel(
       for (int t = lane; t < k; t += 64) dst[t] = sel[row * STRIDE + t];
     }
   }
+  if constexpr (PROBS) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float2 p = ms_group16(pm[e], ps[e]);
+      const int row = i0 + rowbase + 4 * qd + e;
+      if (r == 0 && row < nq) ms[(long)row * n_spans + span] = p;
+    }
+  }
 }
 
 // One wave per query row: the k best of the row's n_spans * k partial results.
+// PROBS (TOPK_PROBS_*): also out_prob [nq][k].  Softmax: the row's n_spans pairs give M (exact) and
+// S = sum s_j exp(m_j - M), each lane adding its spans in ascending order, then a fixed add tree; the
+// probability of an entry is expf(l - M) / S, (M, S) goes to out_norm if given.  Sigmoid: sigmoidf_ref of
+// similarity.hip on the entry's logit.  Empty slots get 0.
+template <int PROBS>
 __global__ __launch_bounds__(256) void topk_merge_kernel(const uint2* __restrict__ ws, int nq, int n_spans, int k,
-                                                         int64_t* __restrict__ out_idx, float* __restrict__ out_score) {
+                                                         int64_t* __restrict__ out_idx, float* __restrict__ out_score,
+                                                         const float2* __restrict__ ms, float* __restrict__ out_prob,
+                                                         float* __restrict__ out_norm) {
   __shared__ uint2 sel[4][kTopkMax + CAND2];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int row = blockIdx.x * 4 + wave;
@@ -318,11 +379,31 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const uint2* __restrict
     }
   }
   if (c > 0) compact_row(ent, k, c, lane);
+  float M = -INFINITY, S = 0.f;
+  if constexpr (PROBS == TOPK_PROBS_SOFTMAX) {
+    const float2* pr = ms + (long)row * n_spans;
+    for (int j = lane; j < n_spans; j += 64) M = fmaxf(M, pr[j].x);
+    M = wave_max(M);
+    for (int j = lane; j < n_spans; j += 64) {
+      const float2 p = pr[j];
+      S += p.x == M ? p.y : p.y * expf(p.x - M);
+    }
+    S = wave_sum(S);
+    if (M == INFINITY) S = NAN;  // exp(inf - inf)
+    if (out_norm && lane == 0) {
+      out_norm[2 * (long)row] = M;
+      out_norm[2 * (long)row + 1] = S;
+    }
+  }
   for (int t = lane; t < k; t += 64) {
     const uint2 e = ent[t];
     const bool empty = e.y == kTopkEmptyIndex;
     out_idx[(long)row * k + t] = empty ? -1 : (int64_t)e.y;
     out_score[(long)row * k + t] = empty ? -INFINITY : __uint_as_float(e.x);
+    if constexpr (PROBS == TOPK_PROBS_SOFTMAX)
+      out_prob[(long)row * k + t] = empty ? 0.f : expf(__uint_as_float(e.x) - M) / S;
+    if constexpr (PROBS == TOPK_PROBS_SIGMOID)
+      out_prob[(long)row * k + t] = empty ? 0.f : 1.0f / (1.0f + expf(-__uint_as_float(e.x)));
   }
 }
 
@@ -346,11 +427,13 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const uint2* __restrict
 // with no allowed row leaves at once.
 constexpr int NB = 16;
 
-template <int KC, typename GT, bool MASKED>
+//
+// PROBS: as in the wide kernel; the columns of the step past the span are all >= c_end and are not counted.
+template <int KC, typename GT, bool MASKED, bool PROBS>
 __global__ __launch_bounds__(64) void topk_narrow_kernel(const float* __restrict__ qry, const GT* __restrict__ gal,
                                                          int nq, int N, int E, float scale, float bias, int k,
                                                          int span_cols, int n_spans, uint2* __restrict__ ws,
-                                                         const uint32_t* __restrict__ mask) {
+                                                         const uint32_t* __restrict__ mask, float2* __restrict__ ms) {
   typedef typename GalRaw<GT>::type raw_t;
   constexpr int STRIDE = KC + CAND1;
   __shared__ __attribute__((aligned(16))) float stage[2][NB * LDT];  // A | B: [row][k slot qd][k step]
@@ -366,6 +449,8 @@ __global__ __launch_bounds__(64) void topk_narrow_kernel(const float* __restrict
       for (int row = 0; row < nq; ++row) {
         uint2* dst = ws + ((long)row * n_spans + span) * k;
         for (int t = lane; t < k; t += 64) dst[t] = ent_empty();
+        if constexpr (PROBS)
+          if (lane == 0) ms[(long)row * n_spans + span] = make_float2(-INFINITY, 0.f);
       }
       return;
     }
@@ -375,6 +460,7 @@ __global__ __launch_bounds__(64) void topk_narrow_kernel(const float* __restrict
   wave_lds_order();
   const int r = lane & 15, qd = lane >> 4;
   uint64_t thr[4] = {0, 0, 0, 0};  // thresholds of rows 4 * qd + e
+  float pm[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY}, ps[4] = {0.f, 0.f, 0.f, 0.f};  // PROBS: their (m, s)
   // Staging as in the wide kernel, by one wave: lane -> (rows lane / 16 + 4 p, p < 4; k step lane % 16).
   const int srow = lane >> 4, sj = lane & 15;
   const float* pa[4];
@@ -421,6 +507,8 @@ __global__ __launch_bounds__(64) void topk_narrow_kernel(const float* __restrict
       const uint32_t bits = __float_as_uint(fmaf(acc[e], scale, bias));
       const uint64_t key = topk_key(bits, col);
       const bool live = col < c_end && rl < nq && allowed;
+      if constexpr (PROBS)  // rows past nq keep pairs of their own, never written
+        if (col < c_end && allowed) ms_add(pm[e], ps[e], __uint_as_float(bits));
       bool pass = live && key > thr[e];
       uint64_t bal = __ballot(pass);
       if (bal == 0) continue;
@@ -527,33 +615,44 @@ __global__ __launch_bounds__(64) void topk_narrow_kernel(const float* __restrict
     uint2* dst = ws + ((long)row * n_spans + span) * k;
     for (int t = lane; t < k; t += 64) dst[t] = sel[row * STRIDE + t];
   }
+  if constexpr (PROBS) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float2 p = ms_group16(pm[e], ps[e]);
+      if (r == 0 && 4 * qd + e < nq) ms[(long)(4 * qd + e) * n_spans + span] = p;
+    }
+  }
 }
 
-template <int KC, typename GT, bool MASKED>
+template <int KC, typename GT, bool MASKED, bool PROBS>
 void launch_partial(bool narrow, const float* q, int nq, const void* g, int N, int E, float scale, float bias, int k,
-                    const TopkPlan& p, void* ws, const uint32_t* mask, hipStream_t s) {
+                    const TopkPlan& p, void* ws, const uint32_t* mask, float2* ms, hipStream_t s) {
   if (narrow)
-    hipLaunchKernelGGL((topk_narrow_kernel<KC, GT, MASKED>), dim3(p.n_spans), dim3(64), 0, s, q, (const GT*)g, nq, N,
-                       E, scale, bias, k, p.span_cols, p.n_spans, (uint2*)ws, mask);
+    hipLaunchKernelGGL((topk_narrow_kernel<KC, GT, MASKED, PROBS>), dim3(p.n_spans), dim3(64), 0, s, q, (const GT*)g,
+                       nq, N, E, scale, bias, k, p.span_cols, p.n_spans, (uint2*)ws, mask, ms);
   else
-    hipLaunchKernelGGL((topk_partial_kernel<KC, GT, MASKED>), dim3((nq + TB - 1) / TB, p.n_spans), dim3(256), 0, s, q,
-                       (const GT*)g, nq, N, E, scale, bias, k, p.span_cols, p.n_spans, (uint2*)ws, (const uint2*)mask);
+    hipLaunchKernelGGL((topk_partial_kernel<KC, GT, MASKED, PROBS>), dim3((nq + TB - 1) / TB, p.n_spans), dim3(256), 0,
+                       s, q, (const GT*)g, nq, N, E, scale, bias, k, p.span_cols, p.n_spans, (uint2*)ws,
+                       (const uint2*)mask, ms);
 }
 
-template <typename GT, bool MASKED>
+template <typename GT, bool MASKED, bool PROBS>
 void launch_partial_k(bool narrow, const float* q, int nq, const void* g, int N, int E, float scale, float bias, int k,
-                      const TopkPlan& p, void* ws, const uint32_t* mask, hipStream_t s) {
-  if (k <= 16) launch_partial<16, GT, MASKED>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, s);
-  else if (k <= 32) launch_partial<32, GT, MASKED>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, s);
-  else if (k <= 64) launch_partial<64, GT, MASKED>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, s);
-  else launch_partial<128, GT, MASKED>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, s);
+                      const TopkPlan& p, void* ws, const uint32_t* mask, float2* ms, hipStream_t s) {
+  if (k <= 16) launch_partial<16, GT, MASKED, PROBS>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, ms, s);
+  else if (k <= 32) launch_partial<32, GT, MASKED, PROBS>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, ms, s);
+  else if (k <= 64) launch_partial<64, GT, MASKED, PROBS>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, ms, s);
+  else launch_partial<128, GT, MASKED, PROBS>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, ms, s);
 }
 
+// ms: NULL = the kernels without the normaliser (the PROBS = false instantiations)
 template <typename GT>
 void launch_partial_m(bool narrow, const float* q, int nq, const void* g, int N, int E, float scale, float bias, int k,
-                      const TopkPlan& p, void* ws, const uint32_t* mask, hipStream_t s) {
-  if (mask) launch_partial_k<GT, true>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, s);
-  else launch_partial_k<GT, false>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, nullptr, s);
+                      const TopkPlan& p, void* ws, const uint32_t* mask, float2* ms, hipStream_t s) {
+  if (mask && ms) launch_partial_k<GT, true, true>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, ms, s);
+  else if (mask) launch_partial_k<GT, true, false>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, nullptr, s);
+  else if (ms) launch_partial_k<GT, false, true>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, nullptr, ms, s);
+  else launch_partial_k<GT, false, false>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, nullptr, nullptr, s);
 }
 
 // eff[w] = live[w] & allow[w] for the words that hold rows [0, n), bits >= n cleared, zeros up to the end
@@ -689,19 +788,34 @@ TopkPlan topk_plan(long N, int nq, int max_blocks) {
 
 hipError_t launch_topk(const float* q, int nq, const void* g, int dtype, int N, int E, float scale, float bias, int k,
                        const TopkPlan& p, void* ws, const uint32_t* mask, int64_t* out_idx, float* out_score,
-                       hipStream_t s) {
+                       hipStream_t s, const TopkProbs* pr) {
   if (nq <= 0 || N <= 0 || E <= 0 || E % 16 != 0 || k < 1 || k > kTopkMax) return hipErrorInvalidValue;
   if (p.span_cols <= 0 || p.span_cols % TB != 0 || (long)p.n_spans * p.span_cols < N ||
       (long)(p.n_spans - 1) * p.span_cols >= N || (long)p.n_spans * k > INT32_MAX || p.n_spans > 65535)
     return hipErrorInvalidValue;
   if (p.narrow && nq > NB) return hipErrorInvalidValue;
   if (mask && ((uintptr_t)mask & 7)) return hipErrorInvalidValue;
-  if (dtype == TOPK_GAL_F32) launch_partial_m<float>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, s);
-  else if (dtype == TOPK_GAL_F16) launch_partial_m<_Float16>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, s);
-  else if (dtype == TOPK_GAL_BF16) launch_partial_m<__bf16>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, s);
+  const int probs = pr ? pr->activation : TOPK_PROBS_NONE;
+  if (probs != TOPK_PROBS_NONE && probs != TOPK_PROBS_SOFTMAX && probs != TOPK_PROBS_SIGMOID) return hipErrorInvalidValue;
+  if (probs != TOPK_PROBS_NONE && !pr->out_prob) return hipErrorInvalidValue;
+  // softmax: one (m, s) pair per (query row, span) in pr->ms
+  float2* ms = probs == TOPK_PROBS_SOFTMAX ? (float2*)pr->ms : nullptr;
+  if (probs == TOPK_PROBS_SOFTMAX && (!ms || ((uintptr_t)ms & 7) || (long)nq * p.n_spans > pr->ms_pairs))
+    return hipErrorInvalidValue;
+  if (dtype == TOPK_GAL_F32) launch_partial_m<float>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, ms, s);
+  else if (dtype == TOPK_GAL_F16) launch_partial_m<_Float16>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, ms, s);
+  else if (dtype == TOPK_GAL_BF16) launch_partial_m<__bf16>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, ms, s);
   else return hipErrorInvalidValue;
-  hipLaunchKernelGGL(topk_merge_kernel, dim3((nq + 3) / 4), dim3(256), 0, s, (const uint2*)ws, nq, p.n_spans, k,
-                     out_idx, out_score);
+  const dim3 grid((nq + 3) / 4);
+  if (probs == TOPK_PROBS_SOFTMAX)
+    hipLaunchKernelGGL(topk_merge_kernel<TOPK_PROBS_SOFTMAX>, grid, dim3(256), 0, s, (const uint2*)ws, nq, p.n_spans, k,
+                       out_idx, out_score, (const float2*)ms, pr->out_prob, pr->out_norm);
+  else if (probs == TOPK_PROBS_SIGMOID)
+    hipLaunchKernelGGL(topk_merge_kernel<TOPK_PROBS_SIGMOID>, grid, dim3(256), 0, s, (const uint2*)ws, nq, p.n_spans, k,
+                       out_idx, out_score, (const float2*)nullptr, pr->out_prob, (float*)nullptr);
+  else
+    hipLaunchKernelGGL(topk_merge_kernel<TOPK_PROBS_NONE>, grid, dim3(256), 0, s, (const uint2*)ws, nq, p.n_spans, k,
+                       out_idx, out_score, (const float2*)nullptr, (float*)nullptr, (float*)nullptr);
   return hipGetLastError();
 }
 

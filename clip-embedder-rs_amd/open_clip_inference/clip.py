@@ -137,13 +137,40 @@ class Clip:
         """Semantic search (examples/search.rs; rank_images, src/clip.rs:134-170, cut to its k best):
         per text the k best rows of ``index`` as (gallery index, logit), best first, equal logits by
         ascending index.  The logits use the model's logit_scale / logit_bias (defaults 1.0 / 0.0).
-        Logits, not probabilities: a softmax over the gallery needs every score of the row and
-        stays with ``rank_images_many``.  Removed rows never appear; ``allow`` (a bool array
+        Logits, not probabilities: ``rank`` returns the probabilities.  Removed rows never appear; ``allow`` (a bool array
         [len(index)]) restricts the search to the rows where it is True, and a text gets fewer than k
         pairs when fewer rows are allowed."""
         scale, bias = self._scale_bias()
         idx, score = index.search(self.text.embed_texts(texts), k, float(scale), float(bias), allow=allow)
         return [[(int(i), float(s)) for i, s in zip(ri, rs) if i >= 0] for ri, rs in zip(idx, score)]
+
+    def rank(self, index, texts: Sequence[str], k: int, allow=None) -> List[List[Tuple[int, float]]]:
+        """rank_images (src/clip.rs:134-170) against a resident gallery, cut to its k best: per text
+        [(gallery index, probability)], best first, with the model's activation (softmax over all live
+        allowed rows of ``index``, or sigmoid), logit_scale and logit_bias.  The probabilities are
+        those of ``rank_images_many`` over the same rows, without the [images x texts] matrix."""
+        scale, bias = self._scale_bias()
+        idx, _, prob = index.search_probs(self.text.embed_texts(texts), k, float(scale), float(bias),
+                                          self._activation(), allow=allow)
+        return [[(int(i), float(p)) for i, p in zip(ri, rp) if i >= 0] for ri, rp in zip(idx, prob)]
+
+    def build_label_index(self, labels: Sequence[str], dtype="f32"):
+        """Embeds ``labels`` and stores them in an ``EmbeddingIndex`` on the text engine's first device
+        (``dtype`` as for ``build_index``); label i is index i.  For ``classify_topk``."""
+        from .index import EmbeddingIndex
+        embs = self.text.embed_texts(labels)
+        index = EmbeddingIndex(embs.shape[1], len(embs), self.text.session.devices[0], dtype)
+        index.add(embs)
+        return index
+
+    def classify_topk(self, images, label_index, k: int) -> List[List[Tuple[int, float]]]:
+        """classify (src/clip.rs:92-132) for many images against a label index (``build_label_index``),
+        cut to its k best: per image [(label index, probability)], best first, the probabilities those of
+        ``classify_many`` (softmax over all labels of the index, or sigmoid)."""
+        scale, bias = self._scale_bias()
+        idx, _, prob = label_index.search_probs(self.vision.embed_images(images), k, float(scale), float(bias),
+                                                self._activation())
+        return [[(int(i), float(p)) for i, p in zip(ri, rp) if i >= 0] for ri, rp in zip(idx, prob)]
 
     @staticmethod
     def softmax(logits) -> np.ndarray:  # src/clip.rs:172-179 (f32, sequential sum; facade.cpp)

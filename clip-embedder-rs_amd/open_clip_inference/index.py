@@ -14,6 +14,7 @@ from ._lib import check, lib
 
 TOPK_MAX = 128  # CLIPGPU_TOPK_MAX
 DTYPES = {"f32": 0, "f16": 1, "bf16": 2}  # enum clipgpu_index_dtype
+PROB_ACTIVATIONS = {"softmax": 0, "sigmoid": 1}  # CLIPGPU_SIM_SOFTMAX, CLIPGPU_SIM_SIGMOID
 
 
 def pack_allow(allowed) -> np.ndarray:
@@ -39,7 +40,8 @@ class EmbeddingIndex:
     index rounds them to nearest even on the device, and a search returns exactly what an f32 index
     of the rounded rows returns (include/clipgpu.h has the bound on a logit's change).  ``remove``
     marks rows dead without moving the others, ``set_rows`` overwrites rows in place (and revives
-    them), and ``search(..., allow=)`` searches a subset, exactly."""
+    them), and ``search(..., allow=)`` searches a subset, exactly.  ``search_probs`` is the same search
+    with the softmax (over all searched rows) or sigmoid probabilities of the k results."""
 
     def __init__(self, E: int, capacity: int, device: int = 0, dtype: str = "f32"):
         self._h = None
@@ -147,6 +149,18 @@ class EmbeddingIndex:
         index reads the rows four at a time: ``d_rows`` must then be 16-byte aligned."""
         check(lib().clipgpu_index_add_device(self.handle, c_void_p(d_rows), int(n), c_void_p(stream or None)))
 
+    def _allow_words(self, allow):
+        """The bitmap words of ``allow`` (None = no filter), checked before any native call."""
+        if allow is None:
+            return None
+        a = np.asarray(allow)
+        if a.dtype != np.bool_ or a.ndim != 1:
+            raise TypeError(f"allow must be a 1-d bool array, got dtype {a.dtype} with {a.ndim} dimensions")
+        if a.size != len(self):
+            from .error import ShapeError
+            raise ShapeError(f"Shape error: allow must have len(index) = {len(self)} entries, got {a.size}")
+        return pack_allow(a)
+
     def search(self, queries, k: int, logit_scale: float = 1.0, logit_bias: float = 0.0, allow=None
                ) -> Tuple[np.ndarray, np.ndarray]:
         """The k best rows per query, best first: (indices int64 [nq, k], scores f32 [nq, k]) with
@@ -155,15 +169,7 @@ class EmbeddingIndex:
         appear; ``allow`` (a bool array [len(self)], one for all queries) restricts the search to the
         rows where it is True, exactly: the result is that of an index holding only those rows.  Slots
         beyond min(k, live allowed rows) hold (-1, -inf).  1 <= k <= 128."""
-        words = None
-        if allow is not None:
-            a = np.asarray(allow)
-            if a.dtype != np.bool_ or a.ndim != 1:
-                raise TypeError(f"allow must be a 1-d bool array, got dtype {a.dtype} with {a.ndim} dimensions")
-            if a.size != len(self):
-                from .error import ShapeError
-                raise ShapeError(f"Shape error: allow must have len(index) = {len(self)} entries, got {a.size}")
-            words = pack_allow(a)
+        words = self._allow_words(allow)
         q = self._rows(queries, "queries")
         idx = np.empty((q.shape[0], int(k)), np.int64)
         score = np.empty((q.shape[0], int(k)), np.float32)
@@ -181,3 +187,49 @@ class EmbeddingIndex:
                                                          float(logit_scale), float(logit_bias),
                                                          c_void_p(d_allow or None), c_void_p(d_idx), c_void_p(d_score),
                                                          c_void_p(stream or None)))
+
+    @staticmethod
+    def _prob_args(k, activation) -> Tuple[int, int]:
+        """(k, the activation's enum value), checked before any native call."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"k must be an integer, got {type(k).__name__}")
+        if not 1 <= int(k) <= TOPK_MAX:
+            raise ValueError(f"k must be in 1..{TOPK_MAX}, got {int(k)}")
+        if activation not in PROB_ACTIVATIONS:
+            raise ValueError(f"activation must be one of {sorted(PROB_ACTIVATIONS)}, got {activation!r} "
+                             "(logits alone: search)")
+        return int(k), PROB_ACTIVATIONS[activation]
+
+    def search_probs(self, queries, k: int, logit_scale: float = 1.0, logit_bias: float = 0.0,
+                     activation: str = "softmax", allow=None, return_norm: bool = False):
+        """``search`` with the probabilities of the k results: (indices, logits, probs f32 [nq, k]); the
+        first two are exactly what ``search(..., allow=allow)`` returns.  "softmax": exp(l - M) / sum
+        exp(l_i - M) over ALL live allowed rows (not only the k returned), M their largest logit -- what
+        ``similarity(..., "softmax")`` gives over those rows, without the score matrix; "sigmoid":
+        1 / (1 + exp(-l)), bit-identical to ``similarity(..., "sigmoid")``.  Empty slots hold probability
+        0.  ``return_norm=True`` adds a fourth array f32 [nq, 2], (M, S = sum exp(l_i - M)) per query, so
+        that any row's probability is exp(l - M) / S; for "sigmoid" it is NaN (there is no normaliser)."""
+        k, act = self._prob_args(k, activation)
+        words = self._allow_words(allow)
+        q = self._rows(queries, "queries")
+        idx = np.empty((q.shape[0], k), np.int64)
+        score = np.empty((q.shape[0], k), np.float32)
+        prob = np.empty((q.shape[0], k), np.float32)
+        norm = np.full((q.shape[0], 2), np.nan, np.float32) if return_norm else None
+        check(lib().clipgpu_index_search_probs(self.handle, q.ctypes.data, q.shape[0], k, float(logit_scale),
+                                               float(logit_bias), act, None if words is None else words.ctypes.data,
+                                               idx.ctypes.data, score.ctypes.data, prob.ctypes.data,
+                                               None if norm is None else norm.ctypes.data))
+        return (idx, score, prob, norm) if return_norm else (idx, score, prob)
+
+    def search_probs_device(self, d_queries: int, nq: int, k: int, d_idx: int, d_score: int, d_prob: int,
+                            logit_scale: float = 1.0, logit_bias: float = 0.0, activation: str = "softmax",
+                            stream: int = 0, d_allow: int = 0, d_norm: int = 0) -> None:
+        """``search_probs`` on device pointers (as ``search_device``; probs f32 [nq, k] out, ``d_norm`` f32
+        [nq, 2] out or 0 = not wanted, written for "softmax" only), ordered on ``stream``; returns without
+        synchronising."""
+        k, act = self._prob_args(k, activation)
+        check(lib().clipgpu_index_search_probs_device(self.handle, c_void_p(d_queries), int(nq), k, float(logit_scale),
+                                                      float(logit_bias), act, c_void_p(d_allow or None),
+                                                      c_void_p(d_idx), c_void_p(d_score), c_void_p(d_prob),
+                                                      c_void_p(d_norm or None), c_void_p(stream or None)))

@@ -264,8 +264,8 @@ int clipgpu_similarity_device(const float* d_img, int64_t n_img, const float* d_
  * `device` between calls (the *_device embed entry points can feed it without a host round trip);
  * a search returns only the k best rows per query, the [n_q][N] score matrix never exists.
  *   score(i, j) = dot(queries[i], gallery[j]).mul_add(logit_scale, logit_bias) -- bit-identical to
- *     clipgpu_similarity(..., CLIPGPU_SIM_LOGITS) on the same inputs (logits, not probabilities: a
- *     softmax over the gallery needs the whole row and stays with clipgpu_similarity);
+ *     clipgpu_similarity(..., CLIPGPU_SIM_LOGITS) on the same inputs (logits; the probabilities of
+ *     Clip::rank_images / Clip::classify come from clipgpu_index_search_probs, below);
  *   order: descending score, equal scores by ascending gallery index (the reference's stable
  *     sort_by(partial_cmp), src/clip.rs:160-166); +0.0 == -0.0; a NaN score ranks below -inf
  *     (L2-normalised embeddings never produce one).
@@ -334,7 +334,28 @@ int clipgpu_similarity_device(const float* d_img, int64_t n_img, const float* d_
  * only such slots and no error; size == 0 stays "Empty batch".  clipgpu_index_search[_device] are the
  * filtered forms with allow = NULL: they honour removals, and on an index without removed rows they
  * run the kernels they always ran.  The two bitmaps a search needs (live rows; live AND allow) are part
- * of the work area allocated at creation (capacity / 4 bytes together): a search still allocates nothing. */
+ * of the work area allocated at creation (capacity / 4 bytes together): a search still allocates nothing.
+ *
+ * Probabilities.  clipgpu_index_search_probs[_device] are the filtered forms with one more output, what
+ * Clip::rank_images and Clip::classify return (src/clip.rs:92-170) for the k best rows: out_prob [nq][k].
+ * Let A be the live rows that `allow` admits (NULL: every live row) and l_j the logit of row j as above.
+ *   CLIPGPU_SIM_SOFTMAX: p_j = exp(l_j - M) / sum over i in A of exp(l_i - M), M = the largest l_i of A --
+ *     the max-subtracted softmax over ALL rows of A, not over the k results, and over no other row: the
+ *     result is that of an index holding only the rows of A.  The [nq][size] matrix still never exists:
+ *     the kernels keep one running (max, sum) pair per query row beside the top-k selection.  In f32 with
+ *     expf; the relative error of p_j and of the sum against exact arithmetic on the same logits is bounded
+ *     in DESIGN.md (embedding index, probabilities): below 2^-12 up to |l - M| <= 200 and a million rows.
+ *     out_norm (NULL = not wanted) receives (M, S) per query, S = sum exp(l_i - M) >= 1, so that the
+ *     probability of ANY row is exp(l - M) / S (and a sharded gallery can combine its parts).
+ *   CLIPGPU_SIM_SIGMOID: p_j = 1 / (1 + expf(-l_j)), bit-identical to clipgpu_similarity(...,
+ *     CLIPGPU_SIM_SIGMOID) at those entries; out_norm is left untouched.
+ *   CLIPGPU_SIM_LOGITS or an unknown activation: CLIPGPU_ERR_INVALID, before any device call.
+ * out_idx and out_score are exactly those of clipgpu_index_search_filtered, in the same order; the empty
+ * slots beyond min(k, |A|) hold probability 0 (with A empty: every slot, out_norm = (-inf, 0), no error).
+ * A NaN or +inf logit in A makes every softmax probability of that query NaN, as the reference's
+ * exp(x - max) does; -inf logits add nothing (all of A at -inf: NaN, as there).  Mutex, event ordering,
+ * chunking, host staging and "the _device form does not synchronise" are those of the other searches;
+ * the pairs (at most 512 KiB) and the staged outputs are part of the work area allocated at creation. */
 typedef struct clipgpu_index clipgpu_index;
 #define CLIPGPU_TOPK_MAX 128
 enum clipgpu_index_dtype { CLIPGPU_INDEX_F32 = 0, CLIPGPU_INDEX_F16 = 1, CLIPGPU_INDEX_BF16 = 2 };
@@ -360,6 +381,12 @@ int clipgpu_index_search_filtered(clipgpu_index* ix, const float* queries, int64
 int clipgpu_index_search_filtered_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k,
                                          float logit_scale, float logit_bias, const uint32_t* d_allow, int64_t* d_idx,
                                          float* d_score, void* stream);
+int clipgpu_index_search_probs(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, float logit_scale,
+                               float logit_bias, int activation, const uint32_t* allow, int64_t* out_idx,
+                               float* out_score, float* out_prob, float* out_norm);
+int clipgpu_index_search_probs_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k,
+                                      float logit_scale, float logit_bias, int activation, const uint32_t* d_allow,
+                                      int64_t* d_idx, float* d_score, float* d_prob, float* d_norm, void* stream);
 
 /* ---- data-parallel sharding + the RCCL all-gather (north_star: "batches shard
  * data-parallel across the 8 GPUs of one node with an RCCL all-gather over xGMI only for the final

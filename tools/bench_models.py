@@ -365,6 +365,73 @@ def topk_filter_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 16, 256)):
         ix.close()
 
 
+def topk_probs_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 16, 256), dtypes=("f32", "f16")):
+    """What the probabilities cost (clipgpu_index_search_probs_device, softmax, scale 100): three legs
+    alternate in one process, their order rotating from round to round -- the probability search, the plain
+    search, and the same result by the full-matrix path (clipgpu_similarity_device softmax over the gallery
+    of each query into a [Q][N] tensor, then torch.topk of the probabilities: the softmax is monotone, so
+    no gather by the logits' order is needed), which for a 16-bit index runs on the widened rounded gallery.  Per leg the median and the spread of `runs` device-event timings after `warmup`
+    rounds.  The probability search returns the plain search's indices and bit-equal logits; its
+    probabilities are compared with the matrix path's at the same indices (largest relative difference in
+    the line; tests/test_gpu_index_probs.py holds them to the derived bound at small shapes)."""
+    import ctypes
+    from open_clip_inference import EmbeddingIndex
+    torch.manual_seed(0)
+    L = _lib.lib()
+    s = torch.cuda.current_stream().cuda_stream
+    g = torch.nn.functional.normalize(torch.randn(N, E, device="cuda"), dim=1)
+    qs = {Q: torch.nn.functional.normalize(torch.randn(Q, E, device="cuda"), dim=1) for Q in Qs}
+    for dt in dtypes:
+        esz, tdt = INDEX_DTYPES[dt]
+        gw = g if tdt is None else g.to(tdt).float()  # what the index holds, widened
+        ix = EmbeddingIndex(E, N, dtype=dt)
+        ix.add_device(g.data_ptr(), N, s)
+        try:
+            for Q in Qs:
+                q = qs[Q]
+                mat = torch.empty(Q, N, device="cuda")
+                idx = {n: torch.empty((Q, k), dtype=torch.int64, device="cuda") for n in ("probs", "plain")}
+                score = {n: torch.empty((Q, k), device="cuda") for n in ("probs", "plain")}
+                prob, norm = torch.empty((Q, k), device="cuda"), torch.empty((Q, 2), device="cuda")
+                base = {}
+
+                def probs():
+                    ix.search_probs_device(q.data_ptr(), Q, k, idx["probs"].data_ptr(), score["probs"].data_ptr(),
+                                           prob.data_ptr(), 100.0, 0.0, "softmax", s, d_norm=norm.data_ptr())
+
+                def plain():
+                    ix.search_device(q.data_ptr(), Q, k, idx["plain"].data_ptr(), score["plain"].data_ptr(), 100.0, 0.0, s)
+
+                def baseline():
+                    _lib.check(L.clipgpu_similarity_device(ctypes.c_void_p(q.data_ptr()), Q, ctypes.c_void_p(gw.data_ptr()),
+                                                           N, E, 100.0, 0.0, 0, 1, ctypes.c_void_p(mat.data_ptr()),
+                                                           ctypes.c_void_p(s)))
+                    base["prob"], base["idx"] = torch.topk(mat, k, dim=1)
+
+                legs = (("probs", probs), ("plain", plain), ("baseline", baseline))
+                ms = {name: [] for name, _ in legs}
+                for rnd in range(warmup + runs):
+                    for name, fn in legs[rnd % 3:] + legs[:rnd % 3]:  # every leg follows every other equally often
+                        t = _event_ms(fn)
+                        if rnd >= warmup:
+                            ms[name].append(t)
+                assert torch.equal(idx["probs"], idx["plain"])
+                assert torch.equal(score["probs"].view(torch.int32), score["plain"].view(torch.int32))
+                want = torch.gather(mat, 1, idx["probs"])  # the matrix path's probabilities of the same rows
+                rel = float(((prob - want).abs() / want.clamp_min(1e-30)).max())
+                nbytes = N * E * esz
+                out = {"measure": "topk_probs", "Q": Q, "dtype": dt, "N": N, "E": E, "k": k, "runs": runs,
+                       "same_indices_and_logits_as_plain": True, "max_rel_diff_vs_matrix_softmax": float(f"{rel:.3g}"),
+                       "same_top1_as_matrix": bool(torch.equal(base["idx"][:, 0], idx["probs"][:, 0]))}
+                for name, v in ms.items():
+                    out[name] = _stats(v, nbytes)
+                out["probs_over_plain"] = round(out["probs"]["ms_median"] / out["plain"]["ms_median"], 3)
+                out["probs_over_baseline"] = round(out["probs"]["ms_median"] / out["baseline"]["ms_median"], 3)
+                print(json.dumps(out), flush=True)
+        finally:
+            ix.close()
+
+
 def latency_leg(steps=50, warmup=10):
     """Single-item latency (the reference's embed_image / embed_text calls, B = 1) through the
     host entry points: pinned staging + H2D + forward + D2H + synchronise, ViT-B/32."""
@@ -414,6 +481,8 @@ if __name__ == "__main__":
         topk_routes_leg()
     if "topkfilter" in which:  # the filtered search: the cost of the mask and the gain from the skips
         topk_filter_leg()
+    if "topkprobs" in which:  # the probability search against the plain search and the matrix softmax + topk
+        topk_probs_leg()
     if "so400m" in which:
         device_leg("so400m_vision", SO400M_16_SIGLIP2_384_CFG, 0, 128)
     if "h14" in which:
