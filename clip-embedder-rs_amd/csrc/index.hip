@@ -12,12 +12,14 @@
 // Removal and filters.  The authoritative live bitmap is on the host (allocated at the first remove; none
 // = every row live) and mirrored to the work area.  A search with removed rows or an allow bitmap first
 // writes eff = live & allow into the work area (once per call) and runs the masked kernels on it; any
-// other search runs the unmasked kernels as before.
+// other search runs the unmasked kernels.
 //
 // Probabilities (clipgpu_index_search_probs).  The same search with one more output, the softmax over the
 // searched rows or the sigmoid of the k results.  The softmax needs one (max, sum) pair per (query row,
 // span); they live in the work area too (64 pairs per phase-1 block the workspace holds), as do the host
-// form's staged probabilities and (max, sum) rows.  The other searches run the kernels they ran before.
+// form's staged probabilities and (max, sum) rows.
+// Every search entry point fills a SearchReq and a SearchOut for one of two workers, search_device or
+// search_host.  A 16-bit gallery's rows are converted by kernels/gallery.hip on their way in and out.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -48,16 +50,17 @@ struct clipgpu_index {
   int dtype = CLIPGPU_INDEX_F32;  // the gallery's element type
   int64_t esz = 4;                // its bytes
   char* gallery = nullptr;        // [capacity][E] of esz bytes
-  char* work = nullptr;      // ws | staged queries | staged indices | staged scores | live | eff | pairs | staged probs | staged norms
   int ws_blocks = 0;         // phase-1 blocks the workspace holds: min(kMaxBlocks, 4 * 64-row tiles of capacity)
-  float* st_q = nullptr;
-  int64_t* st_idx = nullptr;
-  float* st_score = nullptr;
+  char* work = nullptr;      // one allocation; its regions, in the order carve_work places them:
+  void* d_ws = nullptr;          // the search workspace: ws_blocks * 64 rows of kTopkMax entries
+  float* st_q = nullptr;         // the host form's staged query chunk [kQueryChunk][E],
+  int64_t* st_idx = nullptr;     // its indices [kQueryChunk][kTopkMax]
+  float* st_score = nullptr;     // and scores
   uint32_t* d_live = nullptr;    // the mirror of h_live; bits at and past `size` are ones; read only while n_dead > 0
   uint32_t* d_eff = nullptr;     // the filter of the search in flight: live & allow, whole 64-row tiles
   void* d_ms = nullptr;          // the softmax search in flight: one (max, sum) per (query row, span), 64 * ws_blocks
-  float* st_prob = nullptr;
-  float* st_norm = nullptr;
+  float* st_prob = nullptr;      // the host form's staged probabilities [kQueryChunk][kTopkMax]
+  float* st_norm = nullptr;      // and (max, sum) rows [kQueryChunk][2]
   std::vector<uint32_t> h_live;  // bit i: row i is live; ceil(capacity / 32) words, empty = every row live
   int64_t n_dead = 0;            // cleared bits of h_live below `size`
   float* scratch = nullptr;      // 16-bit index: f32 rows on their way in (add) or out (get_rows); lazy
@@ -71,22 +74,76 @@ namespace {
 void order_after_last(clipgpu_index* ix, hipStream_t s) { HIP_CHECK(hipStreamWaitEvent(s, ix->done, 0)); }
 void mark_last(clipgpu_index* ix, hipStream_t s) { HIP_CHECK(hipEventRecord(ix->done, s)); }
 
+int64_t live_words(int64_t rows) { return (rows + 31) / 32; }
+bool is_live(const clipgpu_index* ix, int64_t i) { return ix->h_live.empty() || ((ix->h_live[i >> 5] >> (i & 31)) & 1u); }
+
+// The next region of the work area: `bytes` at base + off (base NULL: sizes only); off stays a multiple of 256.
+template <typename T>
+T* carve(char* base, size_t& off, size_t bytes) {
+  T* p = base ? (T*)(base + off) : nullptr;
+  off += align256(bytes);
+  return p;
+}
+
+// The work area's layout, once: places the regions at `base` (NULL: nowhere yet) and returns the area's bytes.
+// hipMalloc aligns the base to 256 bytes at least, so every region is; d_eff and d_ms need 8.
+size_t carve_work(clipgpu_index* ix, char* base) {
+  size_t off = 0, chunk = (size_t)kQueryChunk;
+  ix->d_ws = carve<char>(base, off, (size_t)ix->ws_blocks * 64 * kTopkMax * 8);
+  ix->st_q = carve<float>(base, off, chunk * ix->E * 4);
+  ix->st_idx = carve<int64_t>(base, off, chunk * kTopkMax * 8);
+  ix->st_score = carve<float>(base, off, chunk * kTopkMax * 4);
+  ix->d_live = carve<uint32_t>(base, off, (size_t)live_words(ix->capacity) * 4);
+  ix->d_eff = carve<uint32_t>(base, off, (size_t)topk_mask_words(ix->capacity) * 4);
+  ix->d_ms = carve<char>(base, off, (size_t)ix->ws_blocks * 64 * 8);
+  ix->st_prob = carve<float>(base, off, chunk * kTopkMax * 4);
+  ix->st_norm = carve<float>(base, off, chunk * 2 * 4);
+  return off;
+}
+
 void check_add(const clipgpu_index* ix, const float* rows, int64_t n) {
   if (!ix || !rows) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
   if (n <= 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
 }
-
-void check_search(const clipgpu_index* ix, const float* q, int64_t nq, int64_t k, const int64_t* idx,
-                  const float* score) {
-  if (!ix || !q || !idx || !score) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
-  if (nq <= 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
-  if (k < 1 || k > CLIPGPU_TOPK_MAX)
-    throw ClipErr(CLIPGPU_ERR_INVALID, "k must be in 1.." + std::to_string(CLIPGPU_TOPK_MAX) +
-                                           " (clipgpu_similarity gives the whole matrix)");
+char* append_at(const clipgpu_index* ix, int64_t n) {  // where n more rows go; refused if they do not fit
+  if (n > ix->capacity - ix->size) throw ClipErr(CLIPGPU_ERR_INVALID, "index full");
+  return ix->gallery + ix->size * ix->E * ix->esz;
+}
+void check_row_range(const clipgpu_index* ix, int64_t first, int64_t n) {
+  if (first < 0 || n <= 0 || n > ix->size || first > ix->size - n)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "rows out of range (first >= 0, n >= 1, first + n <= size)");
 }
 
-int64_t live_words(int64_t rows) { return (rows + 31) / 32; }
-bool is_live(const clipgpu_index* ix, int64_t i) { return ix->h_live.empty() || ((ix->h_live[i >> 5] >> (i & 31)) & 1u); }
+// One search call: what is asked, and where the results go.  Device pointers for search_device and search_on,
+// host pointers for search_host.  q [nq][E]; probs: TOPK_PROBS_*; allow: the caller's words or NULL.
+struct SearchReq { const float* q; int64_t nq, k; float scale, bias; int probs; const uint32_t* allow; };
+// idx, score, prob: [nq][k], prob for a probability search only; norm: [nq][2] or NULL, written by softmax only.
+struct SearchOut { int64_t* idx; float* score; float* prob; float* norm; };
+
+// The activation of a probability search as the kernels name it, or kBadActivation.
+constexpr int kBadActivation = -1;
+int probs_kind(int activation) {
+  if (activation == CLIPGPU_SIM_SOFTMAX) return TOPK_PROBS_SOFTMAX;
+  return activation == CLIPGPU_SIM_SIGMOID ? TOPK_PROBS_SIGMOID : kBadActivation;
+}
+
+// The refusals that need no lock (the activation before the handle is looked at, NULL arguments, the batch,
+// k, then the probabilities' buffer); then the lock, the empty gallery, and the handle's device.
+std::unique_lock<std::mutex> enter_search(clipgpu_index* ix, const SearchReq& r, const SearchOut& o) {
+  if (r.probs == kBadActivation)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "activation must be CLIPGPU_SIM_SOFTMAX or CLIPGPU_SIM_SIGMOID "
+                                       "(logits: clipgpu_index_search_filtered)");
+  if (!ix || !r.q || !o.idx || !o.score) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+  if (r.nq <= 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
+  if (r.k < 1 || r.k > CLIPGPU_TOPK_MAX)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "k must be in 1.." + std::to_string(CLIPGPU_TOPK_MAX) +
+                                           " (clipgpu_similarity gives the whole matrix)");
+  if (r.probs != TOPK_PROBS_NONE && !o.prob) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+  std::unique_lock<std::mutex> lk(ix->mu);
+  if (ix->size == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");  // an empty gallery
+  HIP_CHECK(hipSetDevice(ix->device));
+  return lk;
+}
 
 // The filter of one search call, written on `s` (which the caller has ordered after the handle's last
 // operation): NULL if nothing filters (no allow bitmap, no removed row), else d_eff = live & allow.
@@ -97,37 +154,72 @@ const uint32_t* build_mask(clipgpu_index* ix, const uint32_t* d_allow, hipStream
   return ix->d_eff;
 }
 
-// Searches d_q [nq][E] in chunks of kQueryChunk rows on `s`, all under one mask.  probs: TOPK_PROBS_NONE, or
-// the probabilities too (d_prob [nq][k]; d_norm [nq][2] or NULL, softmax only).  The span cut is the same with
-// and without them: a launch of B phase-1 blocks writes at most 64 B pairs (wide: 64 rows per block; few-query:
-// 16 rows and at most 4 * ws_blocks spans), which the pair area holds.
-void search_on(clipgpu_index* ix, const float* d_q, int64_t nq, int64_t k, float scale, float bias,
-               const uint32_t* mask, int64_t* d_idx, float* d_score, hipStream_t s, int probs = TOPK_PROBS_NONE,
-               float* d_prob = nullptr, float* d_norm = nullptr) {
-  for (int64_t q0 = 0; q0 < nq; q0 += kQueryChunk) {
-    const int rows = (int)std::min(kQueryChunk, nq - q0);
+// Searches the device rows r.q in chunks of kQueryChunk rows on `s`, all under one mask, into the device buffers
+// of `o`.  The span cut is the same with and without probabilities: a launch of B phase-1 blocks writes at most
+// 64 B pairs (wide: 64 rows per block; few-query: 16 rows, at most 4 * ws_blocks spans), which the pair area holds.
+void search_on(clipgpu_index* ix, const SearchReq& r, const uint32_t* mask, const SearchOut& o, hipStream_t s) {
+  for (int64_t q0 = 0; q0 < r.nq; q0 += kQueryChunk) {
+    const int rows = (int)std::min(kQueryChunk, r.nq - q0);
     const TopkPlan p = topk_plan(ix->size, rows, ix->ws_blocks);  // the route too: few rows, few-query kernel
-    const TopkProbs pr = {probs, ix->d_ms, 64L * ix->ws_blocks, d_prob ? d_prob + q0 * k : nullptr,
-                          d_norm ? d_norm + q0 * 2 : nullptr};
-    HIP_CHECK(launch_topk(d_q + q0 * ix->E, rows, ix->gallery, ix->dtype, (int)ix->size, (int)ix->E, scale, bias,
-                         (int)k, p, ix->work, mask, d_idx + q0 * k, d_score + q0 * k, s,
-                         probs == TOPK_PROBS_NONE ? nullptr : &pr));
+    HIP_CHECK(launch_topk({r.q + q0 * ix->E, rows, ix->gallery, ix->dtype, (int)ix->size, (int)ix->E, r.scale, r.bias,
+                           (int)r.k, p, ix->d_ws, mask, o.idx + q0 * r.k, o.score + q0 * r.k, r.probs, ix->d_ms,
+                           64L * ix->ws_blocks, o.prob ? o.prob + q0 * r.k : nullptr,
+                           o.norm ? o.norm + q0 * 2 : nullptr, s}));
   }
   mark_last(ix, s);
 }
 
-// The activation of a probability search as the kernels name it; refused before any device call.
-int probs_kind(int activation) {
-  if (activation == CLIPGPU_SIM_SOFTMAX) return TOPK_PROBS_SOFTMAX;
-  if (activation == CLIPGPU_SIM_SIGMOID) return TOPK_PROBS_SIGMOID;
-  throw ClipErr(CLIPGPU_ERR_INVALID, "activation must be CLIPGPU_SIM_SOFTMAX or CLIPGPU_SIM_SIGMOID "
-                                     "(logits: clipgpu_index_search_filtered)");
+// The device form: on the caller's stream, ordered after the handle's last operation; r.allow is device words.
+int search_device(clipgpu_index* ix, const SearchReq& r, const SearchOut& o, hipStream_t s) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_search(ix, r, o);
+    order_after_last(ix, s);
+    search_on(ix, r, build_mask(ix, r.allow, s), o, s);
+  });
+}
+
+// The host form: a chunk of queries is staged, searched on the handle's stream and copied back.
+int search_host(clipgpu_index* ix, const SearchReq& r, const SearchOut& o) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_search(ix, r, o);
+    HIP_CHECK(hipEventSynchronize(ix->done));  // the staging buffers and the filter area are free
+    // the caller's words that hold rows [0, size) are staged where the filter is built, once for all chunks
+    if (r.allow) HIP_CHECK(copy_h2d(ix->d_eff, r.allow, (size_t)live_words(ix->size) * 4));
+    const uint32_t* mask = build_mask(ix, r.allow ? ix->d_eff : nullptr, ix->stream);
+    const bool norm = o.norm && r.probs == TOPK_PROBS_SOFTMAX;  // sigmoid writes none: o.norm stays as it is
+    const SearchOut st = {ix->st_idx, ix->st_score, o.prob ? ix->st_prob : nullptr, norm ? ix->st_norm : nullptr};
+    for (int64_t q0 = 0; q0 < r.nq; q0 += kQueryChunk) {
+      const SearchReq c = {ix->st_q, std::min(kQueryChunk, r.nq - q0), r.k, r.scale, r.bias, r.probs, nullptr};
+      HIP_CHECK(copy_h2d(ix->st_q, r.q + q0 * ix->E, (size_t)c.nq * ix->E * 4));
+      search_on(ix, c, mask, st, ix->stream);
+      HIP_CHECK(hipStreamSynchronize(ix->stream));
+      HIP_CHECK(copy_d2h(o.idx + q0 * r.k, st.idx, (size_t)c.nq * r.k * 8));
+      HIP_CHECK(copy_d2h(o.score + q0 * r.k, st.score, (size_t)c.nq * r.k * 4));
+      if (st.prob) HIP_CHECK(copy_d2h(o.prob + q0 * r.k, st.prob, (size_t)c.nq * r.k * 4));
+      if (st.norm) HIP_CHECK(copy_d2h(o.norm + q0 * 2, st.norm, (size_t)c.nq * 2 * 4));
+    }
+  });
 }
 
 // The live words that hold rows [0, size) to the device mirror (synchronous).  Callers hold the mutex
 // and have waited for `done`.
 void upload_live(clipgpu_index* ix) {
   HIP_CHECK(copy_h2d(ix->d_live, ix->h_live.data(), (size_t)live_words(ix->size) * 4));
+}
+
+// Sets (live) or clears the bits of ids[0 .. n) in h_live (which exists), keeps n_dead; true if a bit changed.
+bool mark_rows(clipgpu_index* ix, const int64_t* ids, int64_t n, bool live) {
+  bool changed = false;
+  for (int64_t i = 0; i < n; ++i) {
+    uint32_t& w = ix->h_live[ids[i] >> 5];
+    const uint32_t bit = 1u << (ids[i] & 31);
+    if (((w & bit) != 0) != live) {
+      w ^= bit;
+      ix->n_dead += live ? -1 : 1;
+      changed = true;
+    }
+  }
+  return changed;
 }
 
 void check_ids(const clipgpu_index* ix, const int64_t* ids, int64_t n) {
@@ -139,10 +231,8 @@ void check_ids_in_range(const clipgpu_index* ix, const int64_t* ids, int64_t n) 
     if (ids[i] < 0 || ids[i] >= ix->size) throw ClipErr(CLIPGPU_ERR_INVALID, "id out of range (0 <= id < size)");
 }
 
-// Device scratch for the f32 side of a 16-bit index's host-row add / export, in pieces of at most 64 MiB
-// (one row if a row is larger).  The handle keeps it: allocated at the first use, grown if a later call
-// needs more, freed with the handle.  Callers hold the mutex and have waited for `done`.
-int64_t piece_rows(const clipgpu_index* ix) { return std::max<int64_t>(1, (64LL << 20) / (ix->E * 4)); }
+// Device scratch for host f32 rows on their way into or out of the gallery (add and get_rows of a 16-bit index,
+// set_rows of any): allocated at the first use, grown if a later call needs more, freed with the handle.
 float* scratch_bytes(clipgpu_index* ix, size_t need) {
   if (need > ix->scratch_bytes) {
     if (ix->scratch) HIP_CHECK(hipFree(ix->scratch));
@@ -153,7 +243,17 @@ float* scratch_bytes(clipgpu_index* ix, size_t need) {
   }
   return ix->scratch;
 }
-float* scratch_for(clipgpu_index* ix, int64_t rows) { return scratch_bytes(ix, (size_t)rows * ix->E * 4); }
+
+// n rows through the scratch in pieces of at most 64 MiB of f32 (one row if a row is larger): f(r0, m, f32,
+// behind) for rows [r0, r0 + m), with room for them at f32 and `extra` bytes per row behind (64-byte aligned).
+// Callers hold the mutex and have waited for `done`; f leaves nothing in flight that uses the scratch.
+template <typename F>
+void for_each_piece(clipgpu_index* ix, int64_t n, size_t extra, F f) {
+  const int64_t piece = std::min(n, std::max<int64_t>(1, (64LL << 20) / (ix->E * 4)));
+  const size_t row_bytes = (size_t)piece * ix->E * 4;
+  float* f32 = scratch_bytes(ix, row_bytes + (size_t)piece * extra);
+  for (int64_t r0 = 0; r0 < n; r0 += piece) f(r0, std::min(piece, n - r0), f32, (char*)f32 + row_bytes);
+}
 
 }  // namespace
 
@@ -182,27 +282,15 @@ int clipgpu_index_create_ex(int device, int64_t E, int64_t capacity, int dtype, 
     ix->dtype = dtype;
     ix->esz = topk_gal_bytes(dtype);
     ix->ws_blocks = (int)std::min<int64_t>(kMaxBlocks, 4 * ((capacity + 63) / 64));
-    const size_t ws = align256((size_t)ix->ws_blocks * 64 * kTopkMax * 8);
-    const size_t sq = align256((size_t)kQueryChunk * E * 4), si = align256((size_t)kQueryChunk * kTopkMax * 8);
-    const size_t ss = align256((size_t)kQueryChunk * kTopkMax * 4);
-    const size_t sl = align256((size_t)live_words(capacity) * 4), se = align256((size_t)topk_mask_words(capacity) * 4);
-    const size_t sm = align256((size_t)ix->ws_blocks * 64 * 8), sn = align256((size_t)kQueryChunk * 2 * 4);
     hipError_t err = hipMalloc((void**)&ix->gallery, (size_t)capacity * E * ix->esz);
-    if (err == hipSuccess) err = hipMalloc((void**)&ix->work, ws + sq + si + ss + sl + se + sm + ss + sn);
+    if (err == hipSuccess) err = hipMalloc((void**)&ix->work, carve_work(ix, nullptr));
     if (err == hipSuccess) err = hipStreamCreateWithFlags(&ix->stream, hipStreamNonBlocking);
     if (err == hipSuccess) err = hipEventCreateWithFlags(&ix->done, hipEventDisableTiming);
     if (err != hipSuccess) {
       clipgpu_index_destroy(ix);
       HIP_CHECK(err);
     }
-    ix->st_q = (float*)(ix->work + ws);
-    ix->st_idx = (int64_t*)(ix->work + ws + sq);
-    ix->st_score = (float*)(ix->work + ws + sq + si);
-    ix->d_live = (uint32_t*)(ix->work + ws + sq + si + ss);
-    ix->d_eff = (uint32_t*)(ix->work + ws + sq + si + ss + sl);
-    ix->d_ms = ix->work + ws + sq + si + ss + sl + se;
-    ix->st_prob = (float*)(ix->work + ws + sq + si + ss + sl + se + sm);
-    ix->st_norm = (float*)(ix->work + ws + sq + si + ss + sl + se + sm + ss);
+    carve_work(ix, ix->work);
     *out = ix;
   });
 }
@@ -247,8 +335,7 @@ int clipgpu_index_get_live(clipgpu_index* ix, int64_t first, int64_t n, uint8_t*
   return guarded([&]() {
     if (!ix || !out) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
     std::lock_guard<std::mutex> lk(ix->mu);
-    if (first < 0 || n <= 0 || n > ix->size || first > ix->size - n)
-      throw ClipErr(CLIPGPU_ERR_INVALID, "rows out of range (first >= 0, n >= 1, first + n <= size)");
+    check_row_range(ix, first, n);
     for (int64_t i = 0; i < n; ++i) out[i] = is_live(ix, first + i) ? 1 : 0;
   });
 }
@@ -266,17 +353,7 @@ int clipgpu_index_remove(clipgpu_index* ix, const int64_t* ids, int64_t n) {
       HIP_CHECK(hipMemsetAsync(ix->d_live, 0xff, (size_t)live_words(ix->capacity) * 4, ix->stream));
       HIP_CHECK(hipStreamSynchronize(ix->stream));
     }
-    bool changed = false;
-    for (int64_t i = 0; i < n; ++i) {
-      uint32_t& w = ix->h_live[ids[i] >> 5];
-      const uint32_t bit = 1u << (ids[i] & 31);
-      if (w & bit) {
-        w &= ~bit;
-        ++ix->n_dead;
-        changed = true;
-      }
-    }
-    if (changed) upload_live(ix);
+    if (mark_rows(ix, ids, n, false)) upload_live(ix);
     mark_last(ix, ix->stream);
   });
 }
@@ -287,41 +364,20 @@ int clipgpu_index_set_rows(clipgpu_index* ix, const int64_t* ids, const float* r
     if (!rows && n > 0) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
     std::lock_guard<std::mutex> lk(ix->mu);
     check_ids_in_range(ix, ids, n);
-    {
-      std::vector<int64_t> sorted(ids, ids + n);
-      std::sort(sorted.begin(), sorted.end());
-      if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
-        throw ClipErr(CLIPGPU_ERR_INVALID, "duplicate id");
-    }
+    std::vector<int64_t> sorted(ids, ids + n);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw ClipErr(CLIPGPU_ERR_INVALID, "duplicate id");
     if (n == 0) return;
     HIP_CHECK(hipSetDevice(ix->device));
     HIP_CHECK(hipEventSynchronize(ix->done));
-    // pieces of f32 rows followed by their ids go through the device scratch; a scatter kernel writes
-    // (and for a 16-bit index rounds, as add does) row ids[i]
-    const int64_t piece = std::min(n, piece_rows(ix));
-    const size_t row_bytes = (size_t)piece * ix->E * 4;  // a multiple of 64: the ids behind are aligned
-    float* f32 = scratch_bytes(ix, row_bytes + (size_t)piece * 8);
-    int64_t* d_ids = (int64_t*)((char*)f32 + row_bytes);
-    for (int64_t r0 = 0; r0 < n; r0 += piece) {
-      const int64_t m = std::min(piece, n - r0);
+    // f32 rows and, behind them, their ids go through the scratch; the scatter kernel rounds them as add does
+    for_each_piece(ix, n, 8, [&](int64_t r0, int64_t m, float* f32, void* d_ids) {
       HIP_CHECK(copy_h2d(f32, rows + r0 * ix->E, (size_t)m * ix->E * 4));
       HIP_CHECK(copy_h2d(d_ids, ids + r0, (size_t)m * 8));
-      HIP_CHECK(launch_gal_scatter(ix->dtype, f32, d_ids, ix->gallery, m, (int)ix->E, ix->stream));
+      HIP_CHECK(launch_gal_scatter(ix->dtype, f32, (const int64_t*)d_ids, ix->gallery, m, (int)ix->E, ix->stream));
       HIP_CHECK(hipStreamSynchronize(ix->stream));
-    }
-    if (!ix->h_live.empty()) {  // the rows are live again
-      bool changed = false;
-      for (int64_t i = 0; i < n; ++i) {
-        uint32_t& w = ix->h_live[ids[i] >> 5];
-        const uint32_t bit = 1u << (ids[i] & 31);
-        if (!(w & bit)) {
-          w |= bit;
-          --ix->n_dead;
-          changed = true;
-        }
-      }
-      if (changed) upload_live(ix);
-    }
+    });
+    if (!ix->h_live.empty() && mark_rows(ix, ids, n, true)) upload_live(ix);  // the rows are live again
     mark_last(ix, ix->stream);
   });
 }
@@ -330,11 +386,10 @@ int clipgpu_index_add_device(clipgpu_index* ix, const float* d_rows, int64_t n, 
   return guarded([&]() {
     check_add(ix, d_rows, n);
     std::lock_guard<std::mutex> lk(ix->mu);
-    if (n > ix->capacity - ix->size) throw ClipErr(CLIPGPU_ERR_INVALID, "index full");
+    char* dst = append_at(ix, n);
     HIP_CHECK(hipSetDevice(ix->device));
     hipStream_t s = (hipStream_t)stream;
     order_after_last(ix, s);
-    char* dst = ix->gallery + ix->size * ix->E * ix->esz;
     if (ix->dtype == CLIPGPU_INDEX_F32)
       HIP_CHECK(hipMemcpyAsync(dst, d_rows, (size_t)n * ix->E * 4, hipMemcpyDeviceToDevice, s));
     else
@@ -348,21 +403,17 @@ int clipgpu_index_add(clipgpu_index* ix, const float* rows, int64_t n) {
   return guarded([&]() {
     check_add(ix, rows, n);
     std::lock_guard<std::mutex> lk(ix->mu);
-    if (n > ix->capacity - ix->size) throw ClipErr(CLIPGPU_ERR_INVALID, "index full");
+    char* dst = append_at(ix, n);
     HIP_CHECK(hipSetDevice(ix->device));
     HIP_CHECK(hipEventSynchronize(ix->done));
-    char* dst = ix->gallery + ix->size * ix->E * ix->esz;
     if (ix->dtype == CLIPGPU_INDEX_F32) {
       HIP_CHECK(copy_h2d(dst, rows, (size_t)n * ix->E * 4));
     } else {  // the f32 rows go to device scratch and are rounded there
-      const int64_t piece = std::min(n, piece_rows(ix));
-      float* f32 = scratch_for(ix, piece);
-      for (int64_t r0 = 0; r0 < n; r0 += piece) {
-        const int64_t m = std::min(piece, n - r0);
+      for_each_piece(ix, n, 0, [&](int64_t r0, int64_t m, float* f32, void*) {
         HIP_CHECK(copy_h2d(f32, rows + r0 * ix->E, (size_t)m * ix->E * 4));
         HIP_CHECK(launch_gal_round(ix->dtype, f32, dst + r0 * ix->E * ix->esz, m * ix->E, ix->stream));
         HIP_CHECK(hipStreamSynchronize(ix->stream));
-      }
+      });
     }
     ix->size += n;
   });
@@ -374,8 +425,7 @@ int clipgpu_index_get_rows(clipgpu_index* ix, int64_t first, int64_t n, float* o
   return guarded([&]() {
     if (!ix || !out_rows) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
     std::lock_guard<std::mutex> lk(ix->mu);
-    if (first < 0 || n <= 0 || n > ix->size || first > ix->size - n)
-      throw ClipErr(CLIPGPU_ERR_INVALID, "rows out of range (first >= 0, n >= 1, first + n <= size)");
+    check_row_range(ix, first, n);
     HIP_CHECK(hipSetDevice(ix->device));
     HIP_CHECK(hipEventSynchronize(ix->done));
     const char* src = ix->gallery + first * ix->E * ix->esz;
@@ -383,98 +433,40 @@ int clipgpu_index_get_rows(clipgpu_index* ix, int64_t first, int64_t n, float* o
       HIP_CHECK(copy_d2h(out_rows, src, (size_t)n * ix->E * 4));
       return;
     }
-    const int64_t piece = std::min(n, piece_rows(ix));
-    float* f32 = scratch_for(ix, piece);
-    for (int64_t r0 = 0; r0 < n; r0 += piece) {
-      const int64_t m = std::min(piece, n - r0);
+    for_each_piece(ix, n, 0, [&](int64_t r0, int64_t m, float* f32, void*) {
       HIP_CHECK(launch_gal_widen(ix->dtype, src + r0 * ix->E * ix->esz, f32, m * ix->E, ix->stream));
       HIP_CHECK(hipStreamSynchronize(ix->stream));
       HIP_CHECK(copy_d2h(out_rows + r0 * ix->E, f32, (size_t)m * ix->E * 4));
-    }
+    });
   });
 }
 
+// The six searches: with or without a filter, with or without probabilities, host or device buffers.
 int clipgpu_index_search_filtered_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k,
                                          float logit_scale, float logit_bias, const uint32_t* d_allow, int64_t* d_idx,
                                          float* d_score, void* stream) {
-  return guarded([&]() {
-    check_search(ix, d_queries, nq, k, d_idx, d_score);
-    std::lock_guard<std::mutex> lk(ix->mu);
-    if (ix->size == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");  // an empty gallery
-    HIP_CHECK(hipSetDevice(ix->device));
-    hipStream_t s = (hipStream_t)stream;
-    order_after_last(ix, s);
-    const uint32_t* mask = build_mask(ix, d_allow, s);
-    search_on(ix, d_queries, nq, k, logit_scale, logit_bias, mask, d_idx, d_score, s);
-  });
+  return search_device(ix, {d_queries, nq, k, logit_scale, logit_bias, TOPK_PROBS_NONE, d_allow},
+                       {d_idx, d_score, nullptr, nullptr}, (hipStream_t)stream);
 }
 
 int clipgpu_index_search_filtered(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, float logit_scale,
                                   float logit_bias, const uint32_t* allow, int64_t* out_idx, float* out_score) {
-  return guarded([&]() {
-    check_search(ix, queries, nq, k, out_idx, out_score);
-    std::lock_guard<std::mutex> lk(ix->mu);
-    if (ix->size == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
-    HIP_CHECK(hipSetDevice(ix->device));
-    HIP_CHECK(hipEventSynchronize(ix->done));  // the staging buffers and the filter area are free
-    // the caller's words that hold rows [0, size) are staged where the filter is built, once for all chunks
-    if (allow) HIP_CHECK(copy_h2d(ix->d_eff, allow, (size_t)live_words(ix->size) * 4));
-    const uint32_t* mask = build_mask(ix, allow ? ix->d_eff : nullptr, ix->stream);
-    for (int64_t q0 = 0; q0 < nq; q0 += kQueryChunk) {
-      const int64_t rows = std::min(kQueryChunk, nq - q0);
-      HIP_CHECK(copy_h2d(ix->st_q, queries + q0 * ix->E, (size_t)rows * ix->E * 4));
-      search_on(ix, ix->st_q, rows, k, logit_scale, logit_bias, mask, ix->st_idx, ix->st_score, ix->stream);
-      HIP_CHECK(hipStreamSynchronize(ix->stream));
-      HIP_CHECK(copy_d2h(out_idx + q0 * k, ix->st_idx, (size_t)rows * k * 8));
-      HIP_CHECK(copy_d2h(out_score + q0 * k, ix->st_score, (size_t)rows * k * 4));
-    }
-  });
+  return search_host(ix, {queries, nq, k, logit_scale, logit_bias, TOPK_PROBS_NONE, allow},
+                     {out_idx, out_score, nullptr, nullptr});
 }
 
 int clipgpu_index_search_probs_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k,
                                       float logit_scale, float logit_bias, int activation, const uint32_t* d_allow,
                                       int64_t* d_idx, float* d_score, float* d_prob, float* d_norm, void* stream) {
-  return guarded([&]() {
-    const int probs = probs_kind(activation);
-    check_search(ix, d_queries, nq, k, d_idx, d_score);
-    if (!d_prob) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    if (ix->size == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
-    HIP_CHECK(hipSetDevice(ix->device));
-    hipStream_t s = (hipStream_t)stream;
-    order_after_last(ix, s);
-    const uint32_t* mask = build_mask(ix, d_allow, s);
-    search_on(ix, d_queries, nq, k, logit_scale, logit_bias, mask, d_idx, d_score, s, probs, d_prob,
-              probs == TOPK_PROBS_SOFTMAX ? d_norm : nullptr);
-  });
+  return search_device(ix, {d_queries, nq, k, logit_scale, logit_bias, probs_kind(activation), d_allow},
+                       {d_idx, d_score, d_prob, d_norm}, (hipStream_t)stream);
 }
 
 int clipgpu_index_search_probs(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, float logit_scale,
                                float logit_bias, int activation, const uint32_t* allow, int64_t* out_idx,
                                float* out_score, float* out_prob, float* out_norm) {
-  return guarded([&]() {
-    const int probs = probs_kind(activation);
-    check_search(ix, queries, nq, k, out_idx, out_score);
-    if (!out_prob) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    if (ix->size == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
-    HIP_CHECK(hipSetDevice(ix->device));
-    HIP_CHECK(hipEventSynchronize(ix->done));  // the staging buffers and the filter area are free
-    if (allow) HIP_CHECK(copy_h2d(ix->d_eff, allow, (size_t)live_words(ix->size) * 4));
-    const uint32_t* mask = build_mask(ix, allow ? ix->d_eff : nullptr, ix->stream);
-    const bool norm = out_norm && probs == TOPK_PROBS_SOFTMAX;
-    for (int64_t q0 = 0; q0 < nq; q0 += kQueryChunk) {
-      const int64_t rows = std::min(kQueryChunk, nq - q0);
-      HIP_CHECK(copy_h2d(ix->st_q, queries + q0 * ix->E, (size_t)rows * ix->E * 4));
-      search_on(ix, ix->st_q, rows, k, logit_scale, logit_bias, mask, ix->st_idx, ix->st_score, ix->stream, probs,
-                ix->st_prob, norm ? ix->st_norm : nullptr);
-      HIP_CHECK(hipStreamSynchronize(ix->stream));
-      HIP_CHECK(copy_d2h(out_idx + q0 * k, ix->st_idx, (size_t)rows * k * 8));
-      HIP_CHECK(copy_d2h(out_score + q0 * k, ix->st_score, (size_t)rows * k * 4));
-      HIP_CHECK(copy_d2h(out_prob + q0 * k, ix->st_prob, (size_t)rows * k * 4));
-      if (norm) HIP_CHECK(copy_d2h(out_norm + q0 * 2, ix->st_norm, (size_t)rows * 2 * 4));
-    }
-  });
+  return search_host(ix, {queries, nq, k, logit_scale, logit_bias, probs_kind(activation), allow},
+                     {out_idx, out_score, out_prob, out_norm});
 }
 
 int clipgpu_index_search_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k, float logit_scale,
@@ -489,3 +481,4 @@ int clipgpu_index_search(clipgpu_index* ix, const float* queries, int64_t nq, in
 }
 
 }  // extern "C"
+

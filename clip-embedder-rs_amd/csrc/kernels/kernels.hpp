@@ -194,11 +194,6 @@ constexpr int kTopkMax = 128;
 // The gallery's element type (the values of clipgpu_index_dtype).  A 16-bit element is widened in
 // registers, exactly, so a 16-bit gallery gives the bits an f32 gallery of the widened rows gives.
 enum TopkGal { TOPK_GAL_F32 = 0, TOPK_GAL_F16 = 1, TOPK_GAL_BF16 = 2 };
-int topk_gal_bytes(int dtype);
-// f32 -> f16 / bf16 rows, round to nearest even (f16: subnormals kept, |x| >= 65520 -> inf; NaN stays
-// NaN, -0.0 stays -0.0), and back (exact).  n elements, n % 4 == 0, both sides 16-byte / 8-byte aligned.
-hipError_t launch_gal_round(int dtype, const float* in, void* out, long n, hipStream_t s);
-hipError_t launch_gal_widen(int dtype, const void* in, float* out, long n, hipStream_t s);
 // Phase 1 has two kernels with the same results: the wide one (64-query tiles) and the few-query one (one
 // 16-row tile, one wave per block).  A launch of at most kNarrowRows query rows takes the few-query one;
 // g_topk_route (clipgpu_test_topk_route) overrides: 1 = always wide, 2 = few-query for every nq <= 16.
@@ -214,25 +209,50 @@ struct TopkPlan { int span_cols, n_spans; bool narrow; };
 extern std::atomic<long> g_topk_span_cols;
 extern std::atomic<int> g_topk_route;
 TopkPlan topk_plan(long N, int nq, int max_blocks);
-// mask: NULL (every row, the unmasked kernels) or the filter bitmap of launch_topk_mask (the MASKED
-// kernels): only rows whose bit is set enter a result, out slots beyond min(k, allowed rows) are (-1, -inf).
-// pr: NULL (logits only, the kernels as they were) or the probabilities of the k results, out_prob [nq][k]
-// (0 in the empty slots).  TOPK_PROBS_SOFTMAX: exp(l - M) / S over every row the search counts (in range,
-// allowed), M their largest logit and S = sum exp(l - M), from one (m, s) pair per (query row, span) that
-// the PROBS phase-1 kernels write to ms (8-byte aligned, room for ms_pairs >= nq * n_spans pairs); (M, S)
-// goes to out_norm [nq][2] if given.  TOPK_PROBS_SIGMOID: 1 / (1 + expf(-l)), similarity.hip's expression,
-// in the merge alone (ms, out_norm unused).  DESIGN.md (embedding index) derives the error bound.
+// One search launch.  mask: NULL (every row, the unmasked kernels) or the filter bitmap of launch_topk_mask
+// (the MASKED kernels): only rows whose bit is set enter a result, out slots beyond min(k, allowed rows) are
+// (-1, -inf).
+// probs: TOPK_PROBS_NONE (logits only; the four fields after it are unused) or the probabilities of the k
+// results too, out_prob [nq][k] (0 in the empty slots).  TOPK_PROBS_SOFTMAX: exp(l - M) / S over every row
+// the search counts (in range, allowed), M their largest logit and S = sum exp(l - M), from one (m, s) pair
+// per (query row, span) that the PROBS phase-1 kernels write to ms (8-byte aligned, room for
+// ms_pairs >= nq * n_spans pairs); (M, S) goes to out_norm [nq][2] if given.  TOPK_PROBS_SIGMOID:
+// 1 / (1 + expf(-l)), similarity.hip's expression, in the merge alone (ms, out_norm unused).  DESIGN.md
+// (embedding index) derives the error bound.
 enum TopkProbsKind { TOPK_PROBS_NONE = 0, TOPK_PROBS_SOFTMAX = 1, TOPK_PROBS_SIGMOID = 2 };
-struct TopkProbs { int activation; void* ms; long ms_pairs; float* out_prob; float* out_norm; };
-hipError_t launch_topk(const float* q, int nq, const void* g, int dtype, int N, int E, float scale, float bias, int k,
-                       const TopkPlan& p, void* ws, const uint32_t* mask, int64_t* out_idx, float* out_score,
-                       hipStream_t s, const TopkProbs* pr = nullptr);
+struct TopkArgs {
+  const float* q;  // [nq][E]
+  int nq;
+  const void* g;  // [N][E] of dtype (TopkGal)
+  int dtype, N, E;
+  float scale, bias;
+  int k;
+  TopkPlan plan;
+  void* ws;
+  const uint32_t* mask;
+  int64_t* out_idx;
+  float* out_score;
+  int probs;
+  void* ms;
+  long ms_pairs;
+  float* out_prob;
+  float* out_norm;
+  hipStream_t stream;
+};
+hipError_t launch_topk(const TopkArgs& a);
 // The filter bitmap the MASKED kernels read: row i is allowed iff bit i & 31 of word i >> 5 is set.
 // eff (8-byte aligned, topk_mask_words(n) words: whole 64-column tiles) = live & allow over rows [0, n),
 // bits >= n cleared.  live / allow: device words, NULL = all ones, read in their first ceil(n / 32) words;
 // allow may be eff itself.
 long topk_mask_words(long n);
 hipError_t launch_topk_mask(const uint32_t* live, const uint32_t* allow, uint32_t* eff, long n, hipStream_t s);
+
+// The gallery's storage conversion (kernels/gallery.hip).  Bytes of one element:
+int topk_gal_bytes(int dtype);
+// f32 -> f16 / bf16 rows, round to nearest even (f16: subnormals kept, |x| >= 65520 -> inf; NaN stays
+// NaN, -0.0 stays -0.0), and back (exact).  n elements, n % 4 == 0, both sides 16-byte / 8-byte aligned.
+hipError_t launch_gal_round(int dtype, const float* in, void* out, long n, hipStream_t s);
+hipError_t launch_gal_widen(int dtype, const void* in, float* out, long n, hipStream_t s);
 // Row i of in (f32 [n][E], 16-byte aligned) -> row ids[i] of the gallery, rounded as launch_gal_round
 // rounds (an f32 gallery takes the bits).  ids: device, distinct, inside the gallery.
 hipError_t launch_gal_scatter(int dtype, const float* in, const int64_t* ids, void* gal, long n, int E, hipStream_t s);

@@ -20,28 +20,30 @@
 // selection over the row's n_spans * k workspace entries and writes int64 indices and f32 scores,
 // best first; slots beyond min(k, N) are (-1, -inf).
 //
-// The gallery is stored as f32, f16 or bf16 (TopkGal); a 16-bit element is widened in registers, which
-// is exact, so the dot products run on the same f32 chain over widen(row).  A chunk of at most 16 query
-// rows may take the few-query phase 1 instead (topk_narrow_kernel, below): same bits, same order.
+// The gallery is stored as f32, f16 or bf16 (TopkGal; rounded by kernels/gallery.hip); a 16-bit element is widened
+// in registers (gal4, gallery.hpp), which is exact, so the dot products run on the same f32 chain over widen(row).
+// A chunk of at most 16 query rows may take the few-query phase 1 instead (topk_narrow_kernel, below): same bits, same order.
 //
 // Filtered search (MASKED instantiations of both phase-1 kernels): a device bitmap of uint32 words, row i
 // allowed iff bit i & 31 of word i >> 5 is set, padded with zeros to whole 64-column tiles and 8-byte
 // aligned (mask_eff_kernel builds it: live rows AND the caller's allow bits, bits >= N cleared).  A
 // column whose bit is clear does not pass the ballot, so it never enters a list -- unlike a NaN score,
 // which ranks below -inf but is an entry.  A span with no allowed row hands the merge k empty entries.
-// The MASKED = false instantiations are the kernels as they were: an unfiltered search launches them.
+// The MASKED = false instantiations hold none of this: an unfiltered search launches them.
 //
 // Probabilities (PROBS instantiations of both phase-1 kernels and of the merge): the softmax over every row
 // the search counts needs only a running (max, sum exp(l - max)) pair per query row, kept in registers where
 // the scores already are, written once per (row, span) and combined in the merge, which then also writes
 // exp(l - M) / S for the k results (or their sigmoid, which needs the merge alone).  ms_add / ms_group16
 // below; the error bound is derived in DESIGN.md (embedding index, probabilities).  The PROBS = false
-// instantiations are the kernels as they were.
+// instantiations keep no pair and write none.  Host side, at the end of the file: launch_topk checks its
+// TopkArgs (kernels.hpp) and picks the phase-1 instantiation <KC, GT, MASKED, PROBS> from one table.
 #include <algorithm>
 #include <atomic>
 #include <cstdint>
 
 #include "common.hpp"
+#include "gallery.hpp"
 #include "kernels.hpp"
 #include "topk_key.hpp"
 
@@ -68,17 +70,6 @@ __device__ __forceinline__ uint2 ent_empty() { return make_uint2(kTopkEmptyScore
 __device__ __forceinline__ void wave_lds_order() {
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
-}
-
-// Four consecutive 16-bit gallery elements as f32: one 8-byte load, widened (exactly).
-__device__ __forceinline__ float4 gal4(const _Float16* p) {
-  const f16x4 h = *(const f16x4*)p;
-  return make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
-}
-__device__ __forceinline__ float4 gal4(const __bf16* p) {
-  const uint2 u = *(const uint2*)p;
-  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
-                     __uint_as_float(u.y & 0xffff0000u));
 }
 
 // The same elements as loaded (held in registers while the loads are in flight) and widened when staged.
@@ -497,7 +488,9 @@ __global__ __launch_bounds__(64) void topk_narrow_kernel(const float* __restrict
     float* d = dst + (p * 4 + srow) * LDT + sj;
     d[0] = v.x; d[KQ] = v.y; d[2 * KQ] = v.z; d[3 * KQ] = v.w;
   };
-  // C[row = 4 * qd + e][col = r] of the tile at column cj: the wide kernel's selection, on one column tile
+  // C[row = 4 * qd + e][col = r] of the tile at column cj: the wide kernel's selection, on one column tile.
+  // The ballot / compact / append block is written out a second time on purpose: one shared __forceinline__
+  // function for both kernels was tried and changes the generated code of nearly every instantiation.
   auto select = [&](unsigned cj, const f32x4& acc, bool allowed) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -624,37 +617,6 @@ __global__ __launch_bounds__(64) void topk_narrow_kernel(const float* __restrict
   }
 }
 
-template <int KC, typename GT, bool MASKED, bool PROBS>
-void launch_partial(bool narrow, const float* q, int nq, const void* g, int N, int E, float scale, float bias, int k,
-                    const TopkPlan& p, void* ws, const uint32_t* mask, float2* ms, hipStream_t s) {
-  if (narrow)
-    hipLaunchKernelGGL((topk_narrow_kernel<KC, GT, MASKED, PROBS>), dim3(p.n_spans), dim3(64), 0, s, q, (const GT*)g,
-                       nq, N, E, scale, bias, k, p.span_cols, p.n_spans, (uint2*)ws, mask, ms);
-  else
-    hipLaunchKernelGGL((topk_partial_kernel<KC, GT, MASKED, PROBS>), dim3((nq + TB - 1) / TB, p.n_spans), dim3(256), 0,
-                       s, q, (const GT*)g, nq, N, E, scale, bias, k, p.span_cols, p.n_spans, (uint2*)ws,
-                       (const uint2*)mask, ms);
-}
-
-template <typename GT, bool MASKED, bool PROBS>
-void launch_partial_k(bool narrow, const float* q, int nq, const void* g, int N, int E, float scale, float bias, int k,
-                      const TopkPlan& p, void* ws, const uint32_t* mask, float2* ms, hipStream_t s) {
-  if (k <= 16) launch_partial<16, GT, MASKED, PROBS>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, ms, s);
-  else if (k <= 32) launch_partial<32, GT, MASKED, PROBS>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, ms, s);
-  else if (k <= 64) launch_partial<64, GT, MASKED, PROBS>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, ms, s);
-  else launch_partial<128, GT, MASKED, PROBS>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, ms, s);
-}
-
-// ms: NULL = the kernels without the normaliser (the PROBS = false instantiations)
-template <typename GT>
-void launch_partial_m(bool narrow, const float* q, int nq, const void* g, int N, int E, float scale, float bias, int k,
-                      const TopkPlan& p, void* ws, const uint32_t* mask, float2* ms, hipStream_t s) {
-  if (mask && ms) launch_partial_k<GT, true, true>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, ms, s);
-  else if (mask) launch_partial_k<GT, true, false>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, nullptr, s);
-  else if (ms) launch_partial_k<GT, false, true>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, nullptr, ms, s);
-  else launch_partial_k<GT, false, false>(narrow, q, nq, g, N, E, scale, bias, k, p, ws, nullptr, nullptr, s);
-}
-
 // eff[w] = live[w] & allow[w] for the words that hold rows [0, n), bits >= n cleared, zeros up to the end
 // of the last 64-column tile.  live / allow NULL = all ones; both are read in their first ceil(n / 32)
 // words only.  allow may be eff itself (each thread reads and writes its own word).
@@ -670,91 +632,44 @@ __global__ __launch_bounds__(256) void mask_eff_kernel(const uint32_t* live, con
   }
 }
 
-// ---- 16-bit gallery rows: f32 -> storage (round to nearest even) and back (exact) -------------------
-__device__ __forceinline__ uint32_t round16(float x, _Float16*) {
-  const _Float16 h = (_Float16)x;  // v_cvt_f16_f32: nearest even, subnormals kept, |x| >= 65520 -> inf
-  return (uint32_t) __builtin_bit_cast(uint16_t, h);
-}
-__device__ __forceinline__ uint32_t round16(float x, __bf16*) {
-  const uint32_t b = __float_as_uint(x);
-  if ((b & 0x7fffffffu) > 0x7f800000u) return (b >> 16) | 0x40u;  // NaN stays NaN (quiet), sign kept
-  return (b + 0x7fffu + ((b >> 16) & 1u)) >> 16;                    // carries into the exponent, up to inf
-}
-
-template <typename GT>
-__global__ __launch_bounds__(256) void gal_round_kernel(const float* __restrict__ in, GT* __restrict__ out, long n4) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-    const float4 v = ((const float4*)in)[i];
-    uint2 o;
-    o.x = round16(v.x, (GT*)nullptr) | (round16(v.y, (GT*)nullptr) << 16);
-    o.y = round16(v.z, (GT*)nullptr) | (round16(v.w, (GT*)nullptr) << 16);
-    ((uint2*)out)[i] = o;
-  }
+// ---- launches: phase 1 of one instantiation, the few-query kernel or the wide one as the plan says ----
+template <int KC, typename GT, bool MASKED, bool PROBS>
+void launch_phase1(const TopkArgs& a, float2* ms) {
+  const TopkPlan& p = a.plan;
+  if (p.narrow)
+    hipLaunchKernelGGL((topk_narrow_kernel<KC, GT, MASKED, PROBS>), dim3(p.n_spans), dim3(64), 0, a.stream, a.q,
+                       (const GT*)a.g, a.nq, a.N, a.E, a.scale, a.bias, a.k, p.span_cols, p.n_spans, (uint2*)a.ws, a.mask,
+                       ms);
+  else
+    hipLaunchKernelGGL((topk_partial_kernel<KC, GT, MASKED, PROBS>), dim3((a.nq + TB - 1) / TB, p.n_spans), dim3(256), 0,
+                       a.stream, a.q, (const GT*)a.g, a.nq, a.N, a.E, a.scale, a.bias, a.k, p.span_cols, p.n_spans,
+                       (uint2*)a.ws, (const uint2*)a.mask, ms);
 }
 
-template <typename GT>
-__global__ __launch_bounds__(256) void gal_widen_kernel(const GT* __restrict__ in, float* __restrict__ out, long n4) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256)
-    ((float4*)out)[i] = gal4(in + 4 * i);
+// Every instantiation: [gallery type][MASKED][PROBS][list capacity 16 / 32 / 64 / 128].
+typedef void (*Phase1)(const TopkArgs&, float2*);
+#define PHASE1_KC(GT, M, P) \
+  { launch_phase1<16, GT, M, P>, launch_phase1<32, GT, M, P>, launch_phase1<64, GT, M, P>, launch_phase1<128, GT, M, P> }
+#define PHASE1_GT(GT) \
+  { {PHASE1_KC(GT, false, false), PHASE1_KC(GT, false, true)}, {PHASE1_KC(GT, true, false), PHASE1_KC(GT, true, true)} }
+constexpr Phase1 kPhase1[3][2][2][4] = {PHASE1_GT(float), PHASE1_GT(_Float16), PHASE1_GT(__bf16)};
+static_assert(TOPK_GAL_F32 == 0 && TOPK_GAL_F16 == 1 && TOPK_GAL_BF16 == 2, "the first index of kPhase1");
+
+// The smallest list capacity that holds k, MASKED iff there is a mask, PROBS iff there are pairs to write (ms).
+void dispatch_phase1(const TopkArgs& a, float2* ms) {
+  const int kc = a.k <= 16 ? 0 : a.k <= 32 ? 1 : a.k <= 64 ? 2 : 3;
+  kPhase1[a.dtype][a.mask != nullptr][ms != nullptr][kc](a, ms);
 }
 
-// Row i of `in` (f32 [n][E]) to row ids[i] of the gallery, rounded as gal_round_kernel rounds (an f32
-// gallery takes the bits).  The ids are distinct and inside the gallery (checked by the caller).
-__device__ __forceinline__ void gal_store4(float* out, long i4, float4 v) { ((float4*)out)[i4] = v; }
-template <typename GT> __device__ __forceinline__ void gal_store4(GT* out, long i4, float4 v) {
-  uint2 o;
-  o.x = round16(v.x, (GT*)nullptr) | (round16(v.y, (GT*)nullptr) << 16);
-  o.y = round16(v.z, (GT*)nullptr) | (round16(v.w, (GT*)nullptr) << 16);
-  ((uint2*)out)[i4] = o;
+// Phase 2; the outputs an instantiation does not write are passed as NULL.
+template <int PROBS>
+void launch_merge(const TopkArgs& a, const float2* ms) {
+  hipLaunchKernelGGL(topk_merge_kernel<PROBS>, dim3((a.nq + 3) / 4), dim3(256), 0, a.stream, (const uint2*)a.ws, a.nq,
+                     a.plan.n_spans, a.k, a.out_idx, a.out_score, ms, PROBS == TOPK_PROBS_NONE ? nullptr : a.out_prob,
+                     PROBS == TOPK_PROBS_SOFTMAX ? a.out_norm : nullptr);
 }
-
-template <typename GT>
-__global__ __launch_bounds__(256) void gal_scatter_kernel(const float* __restrict__ in, const int64_t* __restrict__ ids,
-                                                          GT* __restrict__ gal, long n, int E4) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n * E4; i += (long)gridDim.x * 256) {
-    const long row = i / E4, c = i - row * E4;
-    gal_store4(gal, ids[row] * E4 + c, ((const float4*)in)[i]);
-  }
-}
-
-int convert_blocks(long n4) { return (int)std::min<long>((n4 + 255) / 256, 8192); }
 
 }  // namespace
-
-int topk_gal_bytes(int dtype) { return dtype == TOPK_GAL_F32 ? 4 : 2; }
-
-hipError_t launch_gal_round(int dtype, const float* in, void* out, long n, hipStream_t s) {
-  if (n <= 0 || n % 4 || (dtype != TOPK_GAL_F16 && dtype != TOPK_GAL_BF16)) return hipErrorInvalidValue;
-  if (dtype == TOPK_GAL_F16)
-    hipLaunchKernelGGL(gal_round_kernel<_Float16>, dim3(convert_blocks(n / 4)), dim3(256), 0, s, in, (_Float16*)out, n / 4);
-  else
-    hipLaunchKernelGGL(gal_round_kernel<__bf16>, dim3(convert_blocks(n / 4)), dim3(256), 0, s, in, (__bf16*)out, n / 4);
-  return hipGetLastError();
-}
-
-hipError_t launch_gal_widen(int dtype, const void* in, float* out, long n, hipStream_t s) {
-  if (n <= 0 || n % 4 || (dtype != TOPK_GAL_F16 && dtype != TOPK_GAL_BF16)) return hipErrorInvalidValue;
-  if (dtype == TOPK_GAL_F16)
-    hipLaunchKernelGGL(gal_widen_kernel<_Float16>, dim3(convert_blocks(n / 4)), dim3(256), 0, s, (const _Float16*)in, out,
-                       n / 4);
-  else
-    hipLaunchKernelGGL(gal_widen_kernel<__bf16>, dim3(convert_blocks(n / 4)), dim3(256), 0, s, (const __bf16*)in, out,
-                       n / 4);
-  return hipGetLastError();
-}
-
-hipError_t launch_gal_scatter(int dtype, const float* in, const int64_t* ids, void* gal, long n, int E, hipStream_t s) {
-  if (n <= 0 || E <= 0 || E % 4) return hipErrorInvalidValue;
-  const int blocks = convert_blocks(n * (E / 4));
-  if (dtype == TOPK_GAL_F32)
-    hipLaunchKernelGGL(gal_scatter_kernel<float>, dim3(blocks), dim3(256), 0, s, in, ids, (float*)gal, n, E / 4);
-  else if (dtype == TOPK_GAL_F16)
-    hipLaunchKernelGGL(gal_scatter_kernel<_Float16>, dim3(blocks), dim3(256), 0, s, in, ids, (_Float16*)gal, n, E / 4);
-  else if (dtype == TOPK_GAL_BF16)
-    hipLaunchKernelGGL(gal_scatter_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, in, ids, (__bf16*)gal, n, E / 4);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
-}
 
 long topk_mask_words(long n) { return (n + 63) / 64 * 2; }
 
@@ -786,36 +701,25 @@ TopkPlan topk_plan(long N, int nq, int max_blocks) {
   return p;
 }
 
-hipError_t launch_topk(const float* q, int nq, const void* g, int dtype, int N, int E, float scale, float bias, int k,
-                       const TopkPlan& p, void* ws, const uint32_t* mask, int64_t* out_idx, float* out_score,
-                       hipStream_t s, const TopkProbs* pr) {
-  if (nq <= 0 || N <= 0 || E <= 0 || E % 16 != 0 || k < 1 || k > kTopkMax) return hipErrorInvalidValue;
-  if (p.span_cols <= 0 || p.span_cols % TB != 0 || (long)p.n_spans * p.span_cols < N ||
-      (long)(p.n_spans - 1) * p.span_cols >= N || (long)p.n_spans * k > INT32_MAX || p.n_spans > 65535)
+hipError_t launch_topk(const TopkArgs& a) {
+  const TopkPlan& p = a.plan;
+  if (a.nq <= 0 || a.N <= 0 || a.E <= 0 || a.E % 16 != 0 || a.k < 1 || a.k > kTopkMax) return hipErrorInvalidValue;
+  if (p.span_cols <= 0 || p.span_cols % TB != 0 || (long)p.n_spans * p.span_cols < a.N ||
+      (long)(p.n_spans - 1) * p.span_cols >= a.N || (long)p.n_spans * a.k > INT32_MAX || p.n_spans > 65535)
     return hipErrorInvalidValue;
-  if (p.narrow && nq > NB) return hipErrorInvalidValue;
-  if (mask && ((uintptr_t)mask & 7)) return hipErrorInvalidValue;
-  const int probs = pr ? pr->activation : TOPK_PROBS_NONE;
-  if (probs != TOPK_PROBS_NONE && probs != TOPK_PROBS_SOFTMAX && probs != TOPK_PROBS_SIGMOID) return hipErrorInvalidValue;
-  if (probs != TOPK_PROBS_NONE && !pr->out_prob) return hipErrorInvalidValue;
-  // softmax: one (m, s) pair per (query row, span) in pr->ms
-  float2* ms = probs == TOPK_PROBS_SOFTMAX ? (float2*)pr->ms : nullptr;
-  if (probs == TOPK_PROBS_SOFTMAX && (!ms || ((uintptr_t)ms & 7) || (long)nq * p.n_spans > pr->ms_pairs))
+  if (p.narrow && a.nq > NB) return hipErrorInvalidValue;
+  if (a.mask && ((uintptr_t)a.mask & 7)) return hipErrorInvalidValue;
+  if (a.probs < TOPK_PROBS_NONE || a.probs > TOPK_PROBS_SIGMOID) return hipErrorInvalidValue;
+  if (a.probs != TOPK_PROBS_NONE && !a.out_prob) return hipErrorInvalidValue;
+  // softmax: one (m, s) pair per (query row, span) in a.ms
+  float2* ms = a.probs == TOPK_PROBS_SOFTMAX ? (float2*)a.ms : nullptr;
+  if (a.probs == TOPK_PROBS_SOFTMAX && (!ms || ((uintptr_t)ms & 7) || (long)a.nq * p.n_spans > a.ms_pairs))
     return hipErrorInvalidValue;
-  if (dtype == TOPK_GAL_F32) launch_partial_m<float>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, ms, s);
-  else if (dtype == TOPK_GAL_F16) launch_partial_m<_Float16>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, ms, s);
-  else if (dtype == TOPK_GAL_BF16) launch_partial_m<__bf16>(p.narrow, q, nq, g, N, E, scale, bias, k, p, ws, mask, ms, s);
-  else return hipErrorInvalidValue;
-  const dim3 grid((nq + 3) / 4);
-  if (probs == TOPK_PROBS_SOFTMAX)
-    hipLaunchKernelGGL(topk_merge_kernel<TOPK_PROBS_SOFTMAX>, grid, dim3(256), 0, s, (const uint2*)ws, nq, p.n_spans, k,
-                       out_idx, out_score, (const float2*)ms, pr->out_prob, pr->out_norm);
-  else if (probs == TOPK_PROBS_SIGMOID)
-    hipLaunchKernelGGL(topk_merge_kernel<TOPK_PROBS_SIGMOID>, grid, dim3(256), 0, s, (const uint2*)ws, nq, p.n_spans, k,
-                       out_idx, out_score, (const float2*)nullptr, pr->out_prob, (float*)nullptr);
-  else
-    hipLaunchKernelGGL(topk_merge_kernel<TOPK_PROBS_NONE>, grid, dim3(256), 0, s, (const uint2*)ws, nq, p.n_spans, k,
-                       out_idx, out_score, (const float2*)nullptr, (float*)nullptr, (float*)nullptr);
+  if (a.dtype != TOPK_GAL_F32 && a.dtype != TOPK_GAL_F16 && a.dtype != TOPK_GAL_BF16) return hipErrorInvalidValue;
+  dispatch_phase1(a, ms);
+  if (a.probs == TOPK_PROBS_SOFTMAX) launch_merge<TOPK_PROBS_SOFTMAX>(a, ms);
+  else if (a.probs == TOPK_PROBS_SIGMOID) launch_merge<TOPK_PROBS_SIGMOID>(a, nullptr);
+  else launch_merge<TOPK_PROBS_NONE>(a, nullptr);
   return hipGetLastError();
 }
 

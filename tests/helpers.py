@@ -27,6 +27,33 @@ def make_model_dir(cfg=VIT_B_32_CFG, seed=1234, tokenizer_json=None, model_confi
     return d
 
 
+GOLD = os.path.join(os.path.dirname(__file__), "golden")
+TOKJ = os.path.join(GOLD, "clip_synth_tokenizer.json")
+
+# the facade tests' model (the tiny config with the committed tokenizer), images and texts
+TEXTS = ["A photo of a cat", "A photo of a dog", "A photo of a beignet", "Café naïve résumé", "",
+         " ".join(["word"] * 40)]
+
+
+def cfg_with_tokenizer(ctx=16):
+    with open(TOKJ, encoding="utf-8") as f:
+        tj = f.read()
+    vocab = len(json.loads(tj)["model"]["vocab"])
+    cfg = json.loads(json.dumps(TINY_CFG))
+    cfg["model_cfg"]["text_cfg"]["vocab_size"] = vocab
+    cfg["model_cfg"]["text_cfg"]["context_length"] = ctx
+    mc = dict(OPENAI_MODEL_CONFIG, vocab_size=vocab)
+    return cfg, tj, mc
+
+
+def images():
+    g = np.load(os.path.join(GOLD, "preprocess_golden.npz"))
+    ims = [g["cat_face_crop"], g["cat_face_224"]]
+    ims += [weights.synth_images_u8(h * 1000 + w, 1, max(h, w))[0][:h, :w].copy()
+            for h, w in ((389, 517), (97, 301))]
+    return ims
+
+
 def specs(cfg):
     return vision_spec_from_cfg(cfg["model_cfg"]), text_spec_from_cfg(cfg["model_cfg"])
 

@@ -1,76 +1,16 @@
-"""The embedding index's storage types without a GPU: the rounding rule of include/clipgpu.h as numpy
-helpers (pinned against torch's casts on an input that holds every special class), the create-time
-errors of clipgpu_index_create_ex, and the route hook's argument check.
+"""The embedding index's storage types without a GPU: the rounding rule of include/clipgpu.h as the numpy
+helpers of tests/index_cases.py (pinned here against torch's casts on an input that holds every special
+class), the create-time errors of clipgpu_index_create_ex, and the route hook's argument check.
 
-tests/test_gpu_index_dtypes.py adds the rows built here to a 16-bit index and compares what the
-device stored with these helpers, bit for bit."""
+tests/test_gpu_index_dtypes.py adds the same rows to a 16-bit index and compares what the device stored
+with these helpers, bit for bit."""
 import ctypes
 
 import numpy as np
 import pytest
 
-E_SPECIAL = 16
-
-
-def round_f16(x):
-    """f32 -> f16 -> f32, round to nearest even; subnormals kept, |x| >= 65520 -> inf."""
-    with np.errstate(over="ignore"):
-        return np.asarray(x, np.float32).astype(np.float16).astype(np.float32)
-
-
-def round_bf16(x):
-    """f32 -> bf16 -> f32 by the usual bit formula: add 0x7fff + (bit 16), cut the low half; a NaN is
-    kept (quiet bit set, so cutting cannot turn it into an infinity)."""
-    b = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
-    r = ((b + 0x7FFF + ((b >> 16) & 1)) >> 16) << 16
-    r = np.where(np.isnan(x), (b & 0xFFFF0000) | 0x00400000, r)
-    return r.astype(np.uint32).view(np.float32).reshape(np.shape(x))
-
-
-ROUND = {"f16": round_f16, "bf16": round_bf16}
-
-
-def nextafter32(x, to):
-    return np.nextafter(np.float32(x), np.float32(to))
-
-
-# name -> values; every class the header's rule speaks of
-SPECIAL = {
-    # exactly halfway between two neighbours of the 16-bit type; the even neighbour is below / above
-    "f16_half_down": [1 + 2.0**-11, -(1 + 2.0**-11), 1024 + 0.5],
-    "f16_half_up": [1 + 3 * 2.0**-11, -(1 + 3 * 2.0**-11), 1025 + 0.5],
-    "bf16_half_down": [1 + 2.0**-8, -(1 + 2.0**-8), 256 + 1.0],
-    "bf16_half_up": [1 + 3 * 2.0**-8, -(1 + 3 * 2.0**-8), 258 + 1.0],
-    # the mantissa is all ones and rounds up: the carry goes into the exponent
-    "f16_carry": [2 - 2.0**-12, -(4 - 2.0**-11), 2 - 2.0**-11],
-    "bf16_carry": [2 - 2.0**-9, -(4 - 2.0**-8), 2 - 2.0**-8],
-    # f16 subnormals: representable ones, one halfway (1.5 * 2^-24 -> 2 * 2^-24), and around 2^-25,
-    # the largest value that still rounds to 0 (the tie goes to the even 0)
-    "f16_subnormal": [2.0**-24, 3 * 2.0**-24, -(2.0**-15), 1023 * 2.0**-24, 1.5 * 2.0**-24, 2.0**-14 - 2.0**-24],
-    "f16_to_zero": [2.0**-25, -(2.0**-25), 2.0**-30],
-    "f16_just_above_zero": [float(nextafter32(2.0**-25, 1)), -float(nextafter32(2.0**-25, 1))],
-    # the largest finite f16, the largest f32 that still rounds to it, the smallest that rounds to inf
-    "f16_max": [65504.0, -65504.0, float(nextafter32(65520.0, 0))],
-    "f16_to_inf": [65520.0, -65520.0, 1e6],
-    "bf16_to_inf": [float(np.finfo(np.float32).max), -float(np.finfo(np.float32).max)],
-    "zeros": [0.0, -0.0],
-    "infs": [np.inf, -np.inf],
-    "nans": [np.nan, float(np.array([0xFFC00001], np.uint32).view(np.float32)[0]),
-             float(np.array([0x7F800001], np.uint32).view(np.float32)[0])],
-}
-
-
-def special_values():
-    return np.concatenate([np.asarray(v, np.float32) for v in SPECIAL.values()])
-
-
-def special_rows():
-    """[n][E_SPECIAL] f32: the special values, then ordinary ones to fill the rows."""
-    v = special_values()
-    rng = np.random.default_rng(42)
-    n = -(-(len(v) + 150) // E_SPECIAL)  # a dozen rows
-    fill = rng.standard_normal(n * E_SPECIAL - len(v)).astype(np.float32) * np.float32(3.0)
-    return np.concatenate([v, fill]).reshape(n, E_SPECIAL)
+from tests.index_cases import E_SPECIAL, ROUND, SPECIAL, nextafter32, round_bf16, round_f16, special_rows, \
+    special_values
 
 
 def neighbours(x, dt):

@@ -9,14 +9,10 @@ import re
 import numpy as np
 import pytest
 
+from tests.index_cases import pattern
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LENGTHS = [0, 1, 31, 32, 33, 64, 65]
-
-
-def pattern(n):
-    """Rows 0, 3, 6, 9, 10, 12, ...: T F F T F F T F in the first byte, no palindrome at any length >= 2."""
-    i = np.arange(n)
-    return (i % 3 == 0) | (i % 7 == 3)
 
 
 def reference_words(a, bitorder="little"):

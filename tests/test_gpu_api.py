@@ -12,23 +12,9 @@ from oracle import clip_ref, facade_ref, preprocess_ref, weights
 from oracle.model_spec import OPENAI_MEAN, OPENAI_MODEL_CONFIG, OPENAI_STD, TINY_CFG, text_spec_from_cfg, \
     vision_spec_from_cfg
 from oracle.tokenizer_ref import ClipTokenizerRef
-from tests.helpers import COS_TOL, make_model_dir
+from tests.helpers import COS_TOL, GOLD, TEXTS, TOKJ, cfg_with_tokenizer, images, make_model_dir
 
 pytestmark = pytest.mark.gpu
-
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
-TOKJ = os.path.join(GOLD, "clip_synth_tokenizer.json")
-
-
-def cfg_with_tokenizer(ctx=16):
-    with open(TOKJ, encoding="utf-8") as f:
-        tj = f.read()
-    vocab = len(json.loads(tj)["model"]["vocab"])
-    cfg = json.loads(json.dumps(TINY_CFG))
-    cfg["model_cfg"]["text_cfg"]["vocab_size"] = vocab
-    cfg["model_cfg"]["text_cfg"]["context_length"] = ctx
-    mc = dict(OPENAI_MODEL_CONFIG, vocab_size=vocab)
-    return cfg, tj, mc
 
 
 @pytest.fixture(scope="module")
@@ -36,14 +22,6 @@ def model():
     cfg, tj, mc = cfg_with_tokenizer()
     d = make_model_dir(cfg, seed=77, tokenizer_json=tj, model_config=mc)
     return cfg, d
-
-
-def images():
-    g = np.load(os.path.join(GOLD, "preprocess_golden.npz"))
-    ims = [g["cat_face_crop"], g["cat_face_224"]]
-    ims += [weights.synth_images_u8(h * 1000 + w, 1, max(h, w))[0][:h, :w].copy()
-            for h, w in ((389, 517), (97, 301))]
-    return ims
 
 
 def oracle_images(cfg, ims):
@@ -57,10 +35,6 @@ def oracle_texts(cfg, texts):
     tok = ClipTokenizerRef(TOKJ, t.context_length, 0)
     ids = np.array([tok.encode(x)[0] for x in texts], np.int64)
     return clip_ref.encode_text(weights.text_weights(t, 77), t, ids)
-
-
-TEXTS = ["A photo of a cat", "A photo of a dog", "A photo of a beignet", "Café naïve résumé", "",
-         " ".join(["word"] * 40)]
 
 
 def test_vision_embedder_end_to_end(model):

@@ -1,41 +1,19 @@
 """A 16-bit embedding index (EmbeddingIndex(dtype="f16" / "bf16")) on the GPU.  The contract of
 include/clipgpu.h: rows are rounded to nearest even on the device, and a search returns exactly what
-the f32 path returns on widen(round(rows)).  So the expected result is tests/test_gpu_topk.py's
+the f32 path returns on widen(round(rows)).  So the expected result is tests/index_cases.py's
 `expected` (the full logits matrix, stably sorted) on the numpy-rounded gallery, and every comparison
 is == on indices and on uint32 views of scores."""
 import ctypes
-from contextlib import contextmanager
 
 import numpy as np
 import pytest
 
-from tests.test_cpu_index_dtypes import ROUND, special_rows
-from tests.test_gpu_topk import assert_same, expected, span_cols, tied_gallery, unit_rows
+from tests.index_cases import ROUND, assert_same, bits_equal_with_nans, expected, route, routes_for, search16, \
+    span_cols, special_rows, tied_gallery, unit_rows
 
 pytestmark = pytest.mark.gpu
 
 CODES = {"f32": 0, "f16": 1, "bf16": 2}
-
-
-@contextmanager
-def route(r):
-    from open_clip_inference import _lib
-    _lib.check(_lib.lib().clipgpu_test_topk_route(r))
-    try:
-        yield
-    finally:
-        _lib.check(_lib.lib().clipgpu_test_topk_route(0))
-
-
-def routes_for(Q):
-    """Both phase-1 kernels where the few-query one can run, else the default dispatch."""
-    return (1, 2) if Q <= 16 else (0,)
-
-
-def bits_equal_with_nans(got, want):
-    nan = np.isnan(want)
-    assert np.array_equal(np.isnan(got), nan)
-    assert np.array_equal(got.view(np.uint32)[~nan], want.view(np.uint32)[~nan])
 
 
 @pytest.mark.parametrize("dt", ["f16", "bf16"])
@@ -69,13 +47,6 @@ def test_an_f32_index_returns_its_rows_unchanged():
         ix.add(x)
         bits_equal_with_nans(ix.rows(), x)
         bits_equal_with_nans(ix.rows(2, 3), x[2:5])
-
-
-def search16(q, g, k, dt, scale=100.0, bias=0.0):
-    from open_clip_inference import EmbeddingIndex
-    with EmbeddingIndex(g.shape[1], len(g), dtype=dt) as ix:
-        ix.add(g)
-        return ix.search(q, k, scale, bias)
 
 
 SHAPES = [(1, 1, 16, 1), (3, 64, 64, 64), (1, 5, 64, 10), (16, 129, 48, 7), (17, 1000, 80, 20), (70, 4097, 512, 10),
@@ -115,7 +86,7 @@ def test_the_rounding_is_real(dt):
     """A build that quietly stored f32 would pass every comparison against itself: the 16-bit scores
     must differ from the F32 index's in nearly every entry (the rounded rows differ from the f32 rows in
     nearly every element, checked on the host first)."""
-    from tests.test_gpu_topk import search_once
+    from tests.index_cases import search_once
     Q, N, E, k = 70, 4097, 512, 10
     rng = np.random.default_rng(1000 * Q + N)
     q, g = unit_rows(rng, Q, E), unit_rows(rng, N, E)
@@ -183,7 +154,7 @@ def test_handle_semantics_of_a_16_bit_index():
 def test_clip_build_index_f16():
     from open_clip_inference import Clip
     from tests.helpers import make_model_dir
-    from tests.test_gpu_api import TEXTS, cfg_with_tokenizer, images
+    from tests.helpers import TEXTS, cfg_with_tokenizer, images
     cfg, tj, mc = cfg_with_tokenizer()
     clip = Clip.from_local_dir(make_model_dir(cfg, seed=77, tokenizer_json=tj, model_config=mc)).build()
     ims = images()

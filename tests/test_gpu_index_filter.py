@@ -12,16 +12,11 @@ import functools
 import numpy as np
 import pytest
 
-from tests.test_gpu_index_dtypes import route
-from tests.test_gpu_topk import assert_same, span_cols, tied_gallery, unit_rows
+from tests.index_cases import assert_same, logits_oracle, padding, route, span_cols, tied_gallery, unit_rows
 
 pytestmark = pytest.mark.gpu
 
 SCALE, BIAS = 100.0, 0.0
-
-
-def padding(Q, k):
-    return np.full((Q, k), -1, np.int64), np.full((Q, k), -np.inf, np.float32)
 
 
 def sub_index_oracle(q, g, allow, k, dt="f32", scale=SCALE, bias=BIAS):
@@ -34,18 +29,6 @@ def sub_index_oracle(q, g, allow, k, dt="f32", scale=SCALE, bias=BIAS):
         ix.add(g[A])
         idx, score = ix.search(q, k, scale, bias)
     return np.where(idx >= 0, A[np.maximum(idx, 0)], -1).astype(np.int64), score
-
-
-def logits_oracle(L, allow, k):
-    """From the full logits matrix: a stable descending sort over the allowed columns."""
-    A = np.flatnonzero(allow)
-    order = np.argsort(-L[:, A], axis=1, kind="stable")[:, :k]
-    idx, score = A[order].astype(np.int64), np.take_along_axis(L[:, A], order, 1)
-    pad = k - idx.shape[1]
-    if pad > 0:
-        pi, ps = padding(len(L), pad)
-        idx, score = np.concatenate([idx, pi], 1), np.concatenate([score, ps], 1)
-    return idx, np.ascontiguousarray(score, dtype=np.float32)
 
 
 @functools.lru_cache(maxsize=None)

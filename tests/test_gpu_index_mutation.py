@@ -6,10 +6,8 @@ the final rows.  Indices are compared with == and scores as uint32 views."""
 import numpy as np
 import pytest
 
-from tests.test_cpu_index_dtypes import ROUND
-from tests.test_gpu_index_dtypes import bits_equal_with_nans, route
-from tests.test_gpu_index_filter import logits_oracle, padding
-from tests.test_gpu_topk import assert_same, search_once, unit_rows
+from tests.index_cases import ROUND, assert_same, bits_equal_with_nans, logits_oracle, padding, route, search_once, \
+    unit_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -192,7 +190,7 @@ def test_set_rows_rounds_as_add_does(dt):
     """The special rows of the storage-type tests (subnormals, the overflow edge, signed zeros, infinities,
     NaN) written by set_rows come back from rows() as numpy's rounding, the bits that add stores."""
     from open_clip_inference import EmbeddingIndex
-    from tests.test_cpu_index_dtypes import special_rows
+    from tests.index_cases import special_rows
     x = special_rows()
     n, Ex = x.shape
     rng = np.random.default_rng(4)

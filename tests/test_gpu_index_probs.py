@@ -14,9 +14,7 @@ import numpy as np
 import pytest
 
 from tests import index_probs_cases as cases
-from tests.test_cpu_index_filter import pattern
-from tests.test_gpu_index_dtypes import route, routes_for
-from tests.test_gpu_topk import assert_same, span_cols
+from tests.index_cases import assert_same, pattern, route, routes_for, span_cols
 
 pytestmark = pytest.mark.gpu
 
@@ -271,13 +269,67 @@ def test_device_form_after_an_add_on_another_stream():
             assert np.array_equal(dp.cpu().numpy().view(np.uint32), np.take_along_axis(P[:17], idx, 1).view(np.uint32))
 
 
+def test_device_forms_run_past_the_first_chunk():
+    """257 queries in the caller's device buffers: one 256-row chunk, then a one-row chunk that takes the
+    few-query route and writes at the offsets q0 * k (indices, logits, probabilities) and q0 * 2 (norm).  All
+    three device forms, on a non-default stream, under removed rows and an allow bitmap, equal the host forms
+    bit for bit in every row (the host forms are held to the oracle at 257 queries above); the sigmoid search
+    leaves d_norm as it was."""
+    import torch
+    from open_clip_inference import EmbeddingIndex
+    from open_clip_inference.index import pack_allow
+    N, Q, k, scale, sentinel = 300, 257, 12, 100.0, 7.0
+    g, q = cases.rows(N, 64, Q)
+    allow = pattern(N)
+    with EmbeddingIndex(64, N) as ix:
+        ix.add(g)
+        ix.remove(np.array([0, 3, 66, 150, N - 1]))
+        plain = ix.search(q, k, scale, 0.0, allow=allow)
+        soft = ix.search_probs(q, k, scale, 0.0, "softmax", allow=allow, return_norm=True)
+        sigm = ix.search_probs(q, k, scale, 0.0, "sigmoid", allow=allow)
+        assert (plain[0][[0, 255, 256]] >= 0).all()  # rows of both chunks hold results
+        s = torch.cuda.Stream()
+        with torch.cuda.stream(s):
+            dq = torch.from_numpy(q.copy()).cuda()
+            da = torch.from_numpy(pack_allow(allow).view(np.int32)).cuda()
+            di = torch.empty((Q, k), dtype=torch.int64, device="cuda")
+            ds, dp = (torch.empty((Q, k), dtype=torch.float32, device="cuda") for _ in range(2))
+            dn = torch.full((Q, 2), sentinel, dtype=torch.float32, device="cuda")
+
+            def bits(*ts):
+                s.synchronize()
+                return [t.cpu().numpy() for t in ts]
+
+            ix.search_device(dq.data_ptr(), Q, k, di.data_ptr(), ds.data_ptr(), scale, 0.0, s.cuda_stream,
+                             d_allow=da.data_ptr())
+            assert_same(bits(di, ds), plain, "search_device")
+            di.fill_(-2)
+            ds.fill_(sentinel)
+            ix.search_probs_device(dq.data_ptr(), Q, k, di.data_ptr(), ds.data_ptr(), dp.data_ptr(), scale, 0.0,
+                                   "softmax", s.cuda_stream, d_allow=da.data_ptr(), d_norm=dn.data_ptr())
+            got = bits(di, ds, dp, dn)
+            assert_same(got[:2], soft[:2], "search_probs_device softmax")
+            assert np.array_equal(got[2].view(np.uint32), soft[2].view(np.uint32))
+            assert np.array_equal(got[3].view(np.uint32), soft[3].view(np.uint32))
+            di.fill_(-2)
+            ds.fill_(sentinel)
+            dp.fill_(sentinel)
+            dn.fill_(sentinel)
+            ix.search_probs_device(dq.data_ptr(), Q, k, di.data_ptr(), ds.data_ptr(), dp.data_ptr(), scale, 0.0,
+                                   "sigmoid", s.cuda_stream, d_allow=da.data_ptr(), d_norm=dn.data_ptr())
+            got = bits(di, ds, dp, dn)
+            assert_same(got[:2], sigm[:2], "search_probs_device sigmoid")
+            assert np.array_equal(got[2].view(np.uint32), sigm[2].view(np.uint32))
+            assert (got[3] == sentinel).all()  # sigmoid leaves d_norm untouched
+
+
 def test_clip_rank_and_classify_topk():
     """The facade on the seeded tiny model: the first k of rank_images_many / classify_many, probabilities
     within B plus the matrix path's own bound."""
     from open_clip_inference import Clip
     from open_clip_inference.engine import similarity
     from tests.helpers import make_model_dir
-    from tests.test_gpu_api import TEXTS, cfg_with_tokenizer, images
+    from tests.helpers import TEXTS, cfg_with_tokenizer, images
     cfg, tj, mc = cfg_with_tokenizer()
     clip = Clip.from_local_dir(make_model_dir(cfg, seed=77, tokenizer_json=tj, model_config=mc)).build()
     ims, labels, k = images(), TEXTS[:4], 3

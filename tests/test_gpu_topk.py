@@ -9,43 +9,9 @@ Indices are compared exactly and scores as uint32 views: there is no tolerance a
 import numpy as np
 import pytest
 
+from tests.index_cases import assert_same, expected, search_once, span_cols, tied_gallery, unit_rows
+
 pytestmark = pytest.mark.gpu
-
-
-def unit_rows(rng, n, E):
-    x = rng.standard_normal((n, E)).astype(np.float32)
-    return x / np.linalg.norm(x, axis=1, keepdims=True)
-
-
-def expected(q, g, k, scale, bias):
-    from open_clip_inference.engine import similarity
-    L = similarity(q, g, scale, bias, "logits", 1)
-    idx = np.argsort(-L, axis=1, kind="stable")[:, :k]
-    score = np.take_along_axis(L, idx, 1)
-    if idx.shape[1] < k:  # fewer rows than k: (-1, -inf) padding
-        pad = k - idx.shape[1]
-        idx = np.concatenate([idx, np.full((len(q), pad), -1, np.int64)], 1)
-        score = np.concatenate([score, np.full((len(q), pad), -np.inf, np.float32)], 1)
-    return idx.astype(np.int64), score
-
-
-def assert_same(got, want, what=""):
-    assert got[0].dtype == np.int64 and got[1].dtype == np.float32
-    assert np.array_equal(got[0], want[0]), what
-    assert np.array_equal(got[1].view(np.uint32), want[1].view(np.uint32)), what
-
-
-def span_cols(cols):
-    from open_clip_inference import _lib
-    _lib.check(_lib.lib().clipgpu_test_topk_span_cols(cols))
-
-
-def search_once(q, g, k, scale=100.0, bias=0.0):
-    from open_clip_inference import EmbeddingIndex
-    with EmbeddingIndex(g.shape[1], len(g)) as ix:
-        ix.add(g)
-        assert len(ix) == len(g)
-        return ix.search(q, k, scale, bias)
 
 
 @pytest.mark.parametrize("Q,N,E,k", [(1, 1, 16, 1), (3, 64, 64, 64), (65, 129, 512, 10), (7, 5000, 1024, 100),
@@ -81,12 +47,6 @@ def test_many_spans_give_the_same_result(cols, N):
         assert_same(search_once(q, g, 20), want, f"span_cols {cols}")
     finally:
         span_cols(0)
-
-
-def tied_gallery(rng, N, E=64):
-    base = unit_rows(rng, 8, E)
-    d = base.astype(np.float64) @ base.astype(np.float64).T
-    return base, base[rng.integers(0, 8, N)], d
 
 
 @pytest.mark.parametrize("scale,bias", [(100.0, 0.0), (-1.0, 0.0), (10.0, -10.0)])
@@ -167,7 +127,7 @@ def test_clip_build_index_and_search():
     from open_clip_inference import Clip
     from open_clip_inference.engine import similarity
     from tests.helpers import make_model_dir
-    from tests.test_gpu_api import TEXTS, cfg_with_tokenizer, images
+    from tests.helpers import TEXTS, cfg_with_tokenizer, images
     cfg, tj, mc = cfg_with_tokenizer()
     clip = Clip.from_local_dir(make_model_dir(cfg, seed=77, tokenizer_json=tj, model_config=mc)).build()
     ims = images()

@@ -5,9 +5,8 @@ be invisible: every comparison is == on indices and on uint32 views of scores.""
 import numpy as np
 import pytest
 
-from tests.test_cpu_index_dtypes import ROUND
-from tests.test_gpu_index_dtypes import route, search16
-from tests.test_gpu_topk import assert_same, expected, search_once, span_cols, tied_gallery, unit_rows
+from tests.index_cases import ROUND, assert_same, expected, route, search16, search_once, span_cols, tied_gallery, \
+    unit_rows
 
 pytestmark = pytest.mark.gpu
 
