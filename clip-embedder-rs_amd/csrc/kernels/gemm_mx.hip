@@ -496,14 +496,18 @@ hipError_t launch_gemm_mx(DType dt, int epi, int act, const MxGemmParams& p, hip
       p.ldws < p.K / 32)
     return hipErrorInvalidValue;
   if ((long)p.N * p.ldw >= (1L << 31)) return hipErrorInvalidValue;
+  if (p.ldo < p.N) return hipErrorInvalidValue;  // every epilogue stores N elements of a row (as launch_gemm)
   if (epi == EPI_STOREQ && (p.outs == nullptr || p.ldo % 16 || p.ldos < p.N / 32)) return hipErrorInvalidValue;
   if (epi == EPI_STORE16 && p.ldo % 8) return hipErrorInvalidValue;
   if ((epi == EPI_RESID || epi == EPI_STORE32) && p.ldo % 4) return hipErrorInvalidValue;
-  if ((long)p.M * p.lda >= (1L << 31)) {
+  if ((long)p.M * p.lda >= (1L << 31) || (g_gemm_chunk_cap > 0 && p.M > g_gemm_chunk_cap)) {
     // 32-bit per-lane staging offsets (as launch_gemm): consecutive row chunks of whole 256-row
-    // tiles, bit-invisible (per-row scales, per-row MFMA chains)
+    // tiles, bit-invisible (per-row scales, per-row MFMA chains).  The test cap of launch_gemm
+    // (g_gemm_chunk_cap, 0 = off) lowers the chunk here too, so the tests reach this loop.
     long chunk = ((1L << 31) - 1) / p.lda;
+    if (g_gemm_chunk_cap > 0) chunk = std::min(chunk, g_gemm_chunk_cap);
     chunk -= chunk % 256;
+    if (chunk <= 0) return hipErrorInvalidValue;
     const long osz = epi == EPI_STORE16 || (epi == EPI_RESID && p.x16) ? 2 : (epi == EPI_STOREQ ? 1 : 4);
     for (long m0 = 0; m0 < p.M; m0 += chunk) {
       MxGemmParams q = p;

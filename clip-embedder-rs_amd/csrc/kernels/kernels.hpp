@@ -294,6 +294,10 @@ enum MxTile {
   MX_TILE_LAST = MX_TILE_128x128,
 };
 // epi: EPI_STORE16 (act), EPI_RESID, EPI_STORE32, EPI_STOREQ (act); N % 32 == 0.
+// Contract, checked before any launch (a violation returns hipErrorInvalidValue): lda, ldw % 16 == 0 and
+// >= K; ldas, ldws % 4 == 0 and >= K / 32; ldo >= N, and ldo % 8 (EPI_STORE16), % 4 (EPI_RESID,
+// EPI_STORE32), % 16 with outs != nullptr and ldos >= N / 32 (EPI_STOREQ).  M past the 32-bit staging
+// offsets (or past g_gemm_chunk_cap, the tests' cap) runs as row chunks of whole 256-row tiles.
 hipError_t launch_gemm_mx(DType dt, int epi, int act, const MxGemmParams& p, hipStream_t s);
 // Rows of f32 (src_dt < 0) or 16-bit (DType) values -> MX-fp8; cols % 32 == 0.
 hipError_t launch_quant_rows(int src_dt, const void* src, long ld, uint8_t* q, long ldq, uint8_t* qs, long ldqs,

@@ -731,6 +731,8 @@ void run_gemm_mx(int dtype, int mode, int act, int64_t M, int64_t N, int64_t K, 
   if (epi == EPI_STOREQ) {
     g.outs = dOs.as<uint8_t>();
     g.ldos = N / 32;
+    up(dO.p, outq, M * N);  // what the caller's buffers hold: a byte the kernel leaves out keeps it
+    up(dOs.p, outs, M * N / 32);
   }
   if (epi == EPI_RESID && resid) up_stream(g.x16, dO.p, resid, M * N);
   launched(launch_gemm_mx(dt, epi, act, g, nullptr), "launch_gemm_mx");
@@ -761,6 +763,38 @@ int clipgpu_test_gemm_mx_at(int dtype, int mode, int act, int64_t M, int64_t N, 
   return guarded([&]() {
     require(mode != 3, "clipgpu_test_gemm_mx_at: modes 0, 1, 2, 4");
     run_gemm_mx(dtype, mode, act, M, N, K, lda, ldw, tile, Aq, As, Wq, Ws, bias, resid, out, nullptr, nullptr);
+  });
+}
+
+int clipgpu_test_gemm_mx_q_at(int dtype, int act, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
+                              int64_t ldo, int64_t ldos, int tile, const uint8_t* Aq, const uint8_t* As,
+                              const uint8_t* Wq, const uint8_t* Ws, const float* bias, uint8_t* outq, uint8_t* outs) {
+  return guarded([&]() {
+    const DType dt = dt_of(dtype);
+    require(M > 0 && N > 0 && K > 0 && K % 128 == 0 && N % 32 == 0 && lda > 0 && ldw > 0 && ldo > 0 && ldos > 0,
+            "bad MX GEMM shape (K % 128 == 0, N % 32 == 0)");
+    require(Aq && As && Wq && Ws && outq, "missing MX GEMM buffer");
+    // the pitches and a null outs go to the launcher as given (its refusals are what is tested); the
+    // device buffers have room for N-wide rows whatever ldo / ldos say
+    DevBuf dA(M * std::max(lda, K)), dAs(M * K / 32), dW(N * std::max(ldw, K)), dWs(N * K / 32), dB(N * 4),
+        dO(M * std::max(ldo, N) + N), dOs(M * std::max(ldos, N / 32) + N / 32);
+    up(dA.p, Aq, M * lda);
+    up(dAs.p, As, M * K / 32);
+    up(dW.p, Wq, N * ldw);
+    up(dWs.p, Ws, N * K / 32);
+    if (bias) up(dB.p, bias, N * 4);
+    up(dO.p, outq, M * ldo);
+    if (outs) up(dOs.p, outs, M * ldos);
+    MxGemmParams g{};
+    g.A = dA.as<uint8_t>(); g.lda = lda; g.As = dAs.as<uint8_t>(); g.ldas = K / 32;
+    g.W = dW.as<uint8_t>(); g.ldw = ldw; g.Ws = dWs.as<uint8_t>(); g.ldws = K / 32;
+    g.bias = bias ? dB.as<float>() : nullptr;
+    g.out = dO.p; g.ldo = ldo; g.outs = outs ? dOs.as<uint8_t>() : nullptr; g.ldos = ldos;
+    g.M = (int)M; g.N = (int)N; g.K = (int)K; g.tile = tile;
+    launched(launch_gemm_mx(dt, EPI_STOREQ, act, g, nullptr), "launch_gemm_mx");
+    HIP_CHECK(hipDeviceSynchronize());
+    down(outq, dO.p, M * ldo);
+    if (outs) down(outs, dOs.p, M * ldos);
   });
 }
 

@@ -96,6 +96,7 @@ _PROTOS = [
     ("clipgpu_test_gemm_lnf_at", c_int, [c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_float, c_int, c_int, c_int, c_void_p]),
     ("clipgpu_test_gemm_mx_at", c_int, [c_int, c_int, c_int] + [c_int64] * 5 + [c_int] + [c_void_p] * 7),
+    ("clipgpu_test_gemm_mx_q_at", c_int, [c_int, c_int] + [c_int64] * 7 + [c_int] + [c_void_p] * 7),
     ("clipgpu_test_gemm_chunk_rows", c_int, [c_int64]),
     ("clipgpu_test_topk_span_cols", c_int, [c_int64]),
     ("clipgpu_test_topk_route", c_int, [c_int]),

@@ -76,9 +76,9 @@ int clipgpu_test_gemm_at(int dtype, int mode, int act, int64_t M, int64_t N, int
 int clipgpu_test_patch_gemm(int dtype, int x16, int cls, int64_t B, int64_t G, int64_t Kp, int64_t D, int tile,
                             const float* rows, const float* W, const float* bias, const float* pos, float* x_inout);
 
-/* Cap the rows of one GEMM launch of launch_gemm's row-chunked path (0 = off: only the 2^31-byte operand
- * limit chunks), process-wide, for every GEMM launched (or graph captured) afterwards: the chunked path
- * of large batches runs at test sizes.  Chunking is bit-invisible. */
+/* Cap the rows of one GEMM launch of launch_gemm's and launch_gemm_mx's row-chunked paths (0 = off: only
+ * the 2^31-byte operand limit chunks), process-wide, for every GEMM launched (or graph captured)
+ * afterwards: the chunked path of large batches runs at test sizes.  Chunking is bit-invisible. */
 int clipgpu_test_gemm_chunk_rows(int64_t rows);
 
 /* qkv: [B*N][3*D] f32 (rounded to 16-bit on upload), D = H * HD (HD in {64, 72, 80}); out: [B*N][D].
@@ -214,6 +214,15 @@ int clipgpu_test_gemm_mx(int dtype, int mode, int act, int64_t M, int64_t N, int
 int clipgpu_test_gemm_mx_at(int dtype, int mode, int act, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
                             int tile, const uint8_t* Aq, const uint8_t* As, const uint8_t* Wq, const uint8_t* Ws,
                             const float* bias, const float* resid, float* out);
+/* Mode 3 (the quantizing epilogue, EPI_STOREQ) with every pitch explicit: Aq [M][lda], Wq [N][ldw], outq
+ * [M][ldo] code bytes, outs [M][ldos] scale bytes.  outq / outs are uploaded before the launch and read back
+ * whole after it, so a byte the kernel does not write keeps the caller's value.  ldo, ldos and a NULL outs
+ * reach the launcher as given: its refusals (ldo % 16, ldo < N, ldos < N/32, outs == NULL) come back as
+ * CLIPGPU_ERR_INVALID with both buffers untouched.  (Mode 3 of clipgpu_test_gemm_mx uploads its dense
+ * outq / outs the same way.) */
+int clipgpu_test_gemm_mx_q_at(int dtype, int act, int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldw,
+                              int64_t ldo, int64_t ldos, int tile, const uint8_t* Aq, const uint8_t* As,
+                              const uint8_t* Wq, const uint8_t* Ws, const float* bias, uint8_t* outq, uint8_t* outs);
 
 /* Device-resident MX GEMM timing (random operands quantized on the device), epi as mode above. */
 int clipgpu_test_gemm_mx_bench(int epi, int act, int64_t M, int64_t N, int64_t K, int tile, int iters,

@@ -8,6 +8,15 @@
   (tools/mx_diag.py) max error ~2^-15 of sum |a||w| on random data, exact on small
   integers); 16-bit epilogue within one 16-bit ulp; the quantizing epilogue (c_fc -> c_proj)
   against the oracle's quantization of the f64 result.
+
+Which MX properties are held how (tests/test_gpu_mx_quant.py, tests/mx_cases.py, tests/test_gpu_gemm.py):
+* exact (==): the quantizing epilogue without activation, the persistent tile walk (three tiles per block),
+  the launcher's row chunks and pitches, the 16-bit / f32 / f16-stream epilogues on integer operands, the
+  stems' MX bytes against launch_ln_rows';
+* per element within a derived interval (no share of mismatches): LayerNorm with MX output (also on this
+  file's test_layernorm_mx data) and the quantizing epilogue with an activation;
+* still bounded here: the scaled MFMA's accumulation on random operands, 2^-12 sum |a||w|, the share
+  thresholds of test_gemm_mx_quantized_out on random operands, and the fp8 engines' cosine bars.
 """
 import numpy as np
 import pytest
@@ -73,6 +82,10 @@ def test_layernorm_mx(D):
     # half the e4m3 spacing at the top binade of the block ([256, 448] * 2^e: spacing 2^(e+5))
     half = np.ldexp(1.0, s.astype(np.int64) - 127 + 4).repeat(32, -1)
     assert np.all(np.abs(deq - ref) <= half * 1.01)
+    # and every scale byte and code within what the f32 LayerNorm's 64 roundings allow (tests/mx_cases.py)
+    from tests import mx_cases as mc
+    amb = mc.check_mx(q, s, *mc.ln_ref_delta(x, w, b), f"LN-MX D {D}")
+    print(f"\n[mx] test_layernorm_mx D {D}: ambiguous blocks {amb[0]:.4%} elements {amb[1]:.4%}")
 
 
 def _mx_operands(rng, M, N, K):

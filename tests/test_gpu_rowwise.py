@@ -12,7 +12,7 @@ the divide, subtract, multiply and fma every f32 result carries fewer than 64 ro
   MAP attention:         1.01 rel |ref| + 1e-4 max|v| (one output rounding + the absolute slack
                          test_gemm_store16_act grants f32 accumulation; the probabilities stay f32)
   l2norm:                32 u |ref|
-  stem sums, gathers, casts, MX bytes, row-loop and batch independence: bit for bit.
+  stem sums, gathers, casts, the stems' MX bytes (both streams), row-loop and batch independence: bit for bit.
 """
 import numpy as np
 import pytest
@@ -132,18 +132,23 @@ def layernorm_mx(x, w, b):
 def check_stem_outputs(run, dtype, x16, D, g1, b1, check_x):
     """The three modes of a stem hook `run(mode) -> (x_out, h, stats, q, qs)`: the stream is the same in
     every mode (check_x judges it), h = ln_1 of the stored row, mode 1's statistics are the stored row's,
-    mode 2's MX bytes equal clipgpu_test_layernorm_mx on the stored row (same arithmetic, same store)."""
+    mode 2's MX bytes equal launch_ln_rows' on the stored row, on both streams (same arithmetic, same store;
+    tests/test_gpu_mx_quant.py holds those bytes to the fp64 LayerNorm), and on the f32 stream
+    clipgpu_test_layernorm_mx's as well."""
     x_out, h, _, _, _ = run(0)
     check_x(x_out)
     rc.check_ln16(dtype, h, x_out, g1, b1)
     x1, _, stats, _, _ = run(1)
     assert np.array_equal(_bits(x1), _bits(x_out))
     rc.check_stats(stats, x_out)
-    if not x16 and D % 32 == 0:
+    if D % 32 == 0:
         x2, _, _, q, qs = run(2)
         assert np.array_equal(_bits(x2), _bits(x_out))
-        rq, rqs = layernorm_mx(x_out, g1, b1)
+        _, _, rq, rqs = ln_rows(dtype, x16, x_out, g1, b1, mx=True)
         assert np.array_equal(q, rq) and np.array_equal(qs, rqs)
+        if not x16:
+            rq, rqs = layernorm_mx(x_out, g1, b1)
+            assert np.array_equal(q, rq) and np.array_equal(qs, rqs)
 
 
 @pytest.mark.parametrize("x16", [0, 1], ids=["x32", "x16"])
