@@ -20,9 +20,16 @@
 // form's staged probabilities and (max, sum) rows.
 // Every search entry point fills a SearchReq and a SearchOut for one of two workers, search_device or
 // search_host.  A 16-bit gallery's rows are converted by kernels/gallery.hip on their way in and out.
+//
+// Range search and self-join (clipgpu_index_range_search[_device], clipgpu_index_self_join; kernels/range.hip).
+// The same chunks of 256 query rows, route and span cut as a search, but every chunk appends its hits to one
+// bounded record buffer behind one 64-bit counter.  The device form writes the caller's buffers; the host forms
+// use a record buffer of the handle's (allocated at the first such call, grown on demand), sort the records on
+// the host and refuse an overflow with the exact total.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstring>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -32,6 +39,7 @@
 #include "hip_check.hpp"
 #include "host/api_util.hpp"
 #include "kernels/kernels.hpp"
+#include "kernels/topk_key.hpp"
 
 using namespace clipgpu;
 
@@ -65,6 +73,8 @@ struct clipgpu_index {
   int64_t n_dead = 0;            // cleared bits of h_live below `size`
   float* scratch = nullptr;      // 16-bit index: f32 rows on their way in (add) or out (get_rows); lazy
   size_t scratch_bytes = 0;
+  char* res = nullptr;           // range search / self-join, host forms: the counter and res_records records; lazy
+  int64_t res_records = 0;
   hipStream_t stream = nullptr;  // the host-buffer forms' stream
   hipEvent_t done = nullptr;     // recorded after every device-side operation
 };
@@ -255,9 +265,183 @@ void for_each_piece(clipgpu_index* ix, int64_t n, size_t extra, F f) {
   for (int64_t r0 = 0; r0 < n; r0 += piece) f(r0, std::min(piece, n - r0), f32, (char*)f32 + row_bytes);
 }
 
+// ---- range search and self-join (kernels/range.hip) ------------------------------------------------------
+// One call: the threshold, the score's scale and bias, and the record capacity the kernels may write up to.
+struct RangeReq { float thr, scale, bias; int64_t cap; };
+// Where the records go, on the device: three arrays of `cap` entries and the 64-bit counter of all hits.
+struct RangeBuf { int32_t* query; int32_t* row; float* score; unsigned long long* total; };
+
+// The refusals that need no lock and no device, in the order the header lists them; then as enter_search.
+// `what` names the capacity argument of the entry point.
+std::unique_lock<std::mutex> enter_range(clipgpu_index* ix, bool null_arg, int64_t nq, const RangeReq& r,
+                                         const char* what) {
+  if (!ix || null_arg) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+  if (nq <= 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
+  if (nq > INT32_MAX) throw ClipErr(CLIPGPU_ERR_INVALID, "too many queries (nq <= 2^31 - 1: a record holds an int32)");
+  if (r.thr != r.thr) throw ClipErr(CLIPGPU_ERR_INVALID, "threshold must not be NaN");
+  if (r.cap < 1 || r.cap > kRangeMaxRecords)
+    throw ClipErr(CLIPGPU_ERR_INVALID, std::string(what) + " must be in 1.." + std::to_string(kRangeMaxRecords) +
+                                           " (2^28), got " + std::to_string(r.cap));
+  std::unique_lock<std::mutex> lk(ix->mu);
+  if (ix->size == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");  // an empty gallery
+  HIP_CHECK(hipSetDevice(ix->device));
+  return lk;
+}
+
+// One launch: `rows` query rows at q (device f32) whose records carry query indices q_off .. q_off + rows.
+// join: they are the gallery rows q_off .. themselves, and the spans start at q_off & ~63.
+void range_chunk(clipgpu_index* ix, const float* q, int rows, int64_t q_off, bool join, const RangeReq& r,
+                 const uint32_t* mask, const RangeBuf& o, hipStream_t s) {
+  const unsigned col0 = join ? (unsigned)(q_off & ~63LL) : 0u;
+  const TopkPlan p = topk_plan(ix->size - col0, rows, ix->ws_blocks);  // the search's route and span cut
+  HIP_CHECK(launch_range({q, rows, ix->gallery, ix->dtype, (int)ix->size, (int)ix->E, r.scale, r.bias, r.thr, p, col0,
+                          mask, (int)q_off, join, (long)r.cap, o.query, o.row, o.score, o.total, s}));
+}
+
+// The host forms' device records: allocated at the first use, grown when a call asks for more, freed with the
+// handle.  A failed allocation is CLIPGPU_ERR_DEVICE and leaves the handle without the buffer, usable.
+// Callers hold the mutex and have waited for `done`.
+RangeBuf result_buffer(clipgpu_index* ix, int64_t records) {
+  if (records > ix->res_records) {
+    if (ix->res) HIP_CHECK(hipFree(ix->res));
+    ix->res = nullptr;
+    ix->res_records = 0;
+    HIP_CHECK(hipMalloc((void**)&ix->res, 256 + 3 * align256((size_t)records * 4)));
+    ix->res_records = records;
+  }
+  size_t off = 0;
+  RangeBuf b;
+  b.total = carve<unsigned long long>(ix->res, off, 8);
+  b.query = carve<int32_t>(ix->res, off, (size_t)ix->res_records * 4);
+  b.row = carve<int32_t>(ix->res, off, (size_t)ix->res_records * 4);
+  b.score = carve<float>(ix->res, off, (size_t)ix->res_records * 4);
+  return b;
+}
+
+struct RangeRec { int32_t query; uint32_t row, bits; };
+
+// After the launches of a host form, on the handle's stream: waits, writes *out_total, refuses an overflow
+// (`what` names the capacity argument) and returns the records sorted by (query, then less(a, b)).
+template <typename Less>
+std::vector<RangeRec> fetch_records(clipgpu_index* ix, const RangeBuf& b, int64_t cap, const char* what,
+                                    int64_t* out_total, Less less) {
+  HIP_CHECK(hipStreamSynchronize(ix->stream));
+  unsigned long long total = 0;
+  HIP_CHECK(copy_d2h(&total, b.total, 8));
+  *out_total = (int64_t)total;
+  if (total > (unsigned long long)cap)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "result overflow: " + std::to_string(total) + " results, " + what + " is " +
+                                           std::to_string(cap) + " (retry with " + what + " >= " +
+                                           std::to_string(total) + ")");
+  const size_t n = (size_t)total;
+  std::vector<int32_t> hq(n), hr(n);
+  std::vector<float> hs(n);
+  if (n) {
+    HIP_CHECK(copy_d2h(hq.data(), b.query, n * 4));
+    HIP_CHECK(copy_d2h(hr.data(), b.row, n * 4));
+    HIP_CHECK(copy_d2h(hs.data(), b.score, n * 4));
+  }
+  std::vector<RangeRec> rec(n);
+  for (size_t i = 0; i < n; ++i) {
+    uint32_t bits;
+    memcpy(&bits, &hs[i], 4);
+    rec[i] = {hq[i], (uint32_t)hr[i], bits};
+  }
+  std::sort(rec.begin(), rec.end(), [&](const RangeRec& a, const RangeRec& c) {
+    return a.query != c.query ? a.query < c.query : less(a, c);
+  });
+  return rec;
+}
+
 }  // namespace
 
 extern "C" {
+
+int clipgpu_index_range_search_device(clipgpu_index* ix, const float* d_queries, int64_t nq, float threshold,
+                                      float logit_scale, float logit_bias, const uint32_t* d_allow, int64_t capacity,
+                                      int32_t* d_out_query, int32_t* d_out_row, float* d_out_score,
+                                      uint64_t* d_out_total, void* stream) {
+  return guarded([&]() {
+    const RangeReq r = {threshold, logit_scale, logit_bias, capacity};
+    const bool null_arg = !d_queries || !d_out_query || !d_out_row || !d_out_score || !d_out_total;
+    const std::unique_lock<std::mutex> lk = enter_range(ix, null_arg, nq, r, "capacity");
+    if ((uintptr_t)d_out_total & 7) throw ClipErr(CLIPGPU_ERR_INVALID, "d_out_total must be 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    order_after_last(ix, s);
+    HIP_CHECK(hipMemsetAsync(d_out_total, 0, 8, s));
+    const uint32_t* mask = build_mask(ix, d_allow, s);
+    const RangeBuf o = {d_out_query, d_out_row, d_out_score, (unsigned long long*)d_out_total};
+    for (int64_t q0 = 0; q0 < nq; q0 += kQueryChunk)
+      range_chunk(ix, d_queries + q0 * ix->E, (int)std::min(kQueryChunk, nq - q0), q0, false, r, mask, o, s);
+    mark_last(ix, s);
+  });
+}
+
+int clipgpu_index_range_search(clipgpu_index* ix, const float* queries, int64_t nq, float threshold, float logit_scale,
+                               float logit_bias, const uint32_t* allow, int64_t max_results, int64_t* out_lims,
+                               int64_t* out_idx, float* out_score, int64_t* out_total) {
+  return guarded([&]() {
+    const RangeReq r = {threshold, logit_scale, logit_bias, max_results};
+    const bool null_arg = !queries || !out_lims || !out_idx || !out_score || !out_total;
+    const std::unique_lock<std::mutex> lk = enter_range(ix, null_arg, nq, r, "max_results");
+    HIP_CHECK(hipEventSynchronize(ix->done));  // the staging buffers, the filter area and the records are free
+    const RangeBuf b = result_buffer(ix, max_results);
+    if (allow) HIP_CHECK(copy_h2d(ix->d_eff, allow, (size_t)live_words(ix->size) * 4));
+    const uint32_t* mask = build_mask(ix, allow ? ix->d_eff : nullptr, ix->stream);
+    HIP_CHECK(hipMemsetAsync(b.total, 0, 8, ix->stream));
+    for (int64_t q0 = 0; q0 < nq; q0 += kQueryChunk) {
+      const int rows = (int)std::min(kQueryChunk, nq - q0);
+      HIP_CHECK(copy_h2d(ix->st_q, queries + q0 * ix->E, (size_t)rows * ix->E * 4));
+      range_chunk(ix, ix->st_q, rows, q0, false, r, mask, b, ix->stream);
+      HIP_CHECK(hipStreamSynchronize(ix->stream));  // the staged chunk is free again
+    }
+    mark_last(ix, ix->stream);
+    // per query: the search's order, descending score, ties by ascending row
+    const std::vector<RangeRec> rec =
+        fetch_records(ix, b, max_results, "max_results", out_total, [](const RangeRec& a, const RangeRec& c) {
+          return topk_key(a.bits, a.row) > topk_key(c.bits, c.row);
+        });
+    size_t at = 0;
+    for (int64_t q = 0; q <= nq; ++q) {
+      while (at < rec.size() && rec[at].query < q) ++at;
+      out_lims[q] = (int64_t)at;
+    }
+    for (size_t i = 0; i < rec.size(); ++i) {
+      out_idx[i] = rec[i].row;
+      memcpy(&out_score[i], &rec[i].bits, 4);
+    }
+  });
+}
+
+int clipgpu_index_self_join(clipgpu_index* ix, float threshold, float logit_scale, float logit_bias,
+                            const uint32_t* allow, int64_t max_pairs, int64_t* out_i, int64_t* out_j, float* out_score,
+                            int64_t* out_total) {
+  return guarded([&]() {
+    const RangeReq r = {threshold, logit_scale, logit_bias, max_pairs};
+    const std::unique_lock<std::mutex> lk = enter_range(ix, !out_i || !out_j || !out_score || !out_total, 1, r, "max_pairs");
+    HIP_CHECK(hipEventSynchronize(ix->done));
+    const RangeBuf b = result_buffer(ix, max_pairs);
+    if (allow) HIP_CHECK(copy_h2d(ix->d_eff, allow, (size_t)live_words(ix->size) * 4));
+    const uint32_t* mask = build_mask(ix, allow ? ix->d_eff : nullptr, ix->stream);
+    HIP_CHECK(hipMemsetAsync(b.total, 0, 8, ix->stream));
+    // chunks of gallery rows are the queries: an f32 gallery's rows in place, a 16-bit gallery's widened into
+    // the staged query chunk (stream order keeps a chunk's widening behind the launch that read the last one)
+    for (int64_t i0 = 0; i0 < ix->size; i0 += kQueryChunk) {
+      const int rows = (int)std::min(kQueryChunk, ix->size - i0);
+      const char* src = ix->gallery + i0 * ix->E * ix->esz;
+      if (ix->dtype != CLIPGPU_INDEX_F32) HIP_CHECK(launch_gal_widen(ix->dtype, src, ix->st_q, rows * ix->E, ix->stream));
+      range_chunk(ix, ix->dtype == CLIPGPU_INDEX_F32 ? (const float*)src : ix->st_q, rows, i0, true, r, mask, b, ix->stream);
+    }
+    mark_last(ix, ix->stream);
+    const std::vector<RangeRec> rec = fetch_records(ix, b, max_pairs, "max_pairs", out_total,
+                                                    [](const RangeRec& a, const RangeRec& c) { return a.row < c.row; });
+    for (size_t i = 0; i < rec.size(); ++i) {
+      out_i[i] = rec[i].query;
+      out_j[i] = rec[i].row;
+      memcpy(&out_score[i], &rec[i].bits, 4);
+    }
+  });
+}
 
 int clipgpu_index_create(int device, int64_t E, int64_t capacity, clipgpu_index** out) {
   return clipgpu_index_create_ex(device, E, capacity, CLIPGPU_INDEX_F32, out);
@@ -304,6 +488,7 @@ void clipgpu_index_destroy(clipgpu_index* ix) {
   }
   if (ix->stream) (void)hipStreamDestroy(ix->stream);
   if (ix->scratch) (void)hipFree(ix->scratch);
+  if (ix->res) (void)hipFree(ix->res);
   if (ix->work) (void)hipFree(ix->work);
   if (ix->gallery) (void)hipFree(ix->gallery);
   delete ix;

@@ -247,6 +247,38 @@ hipError_t launch_topk(const TopkArgs& a);
 long topk_mask_words(long n);
 hipError_t launch_topk_mask(const uint32_t* live, const uint32_t* allow, uint32_t* eff, long n, hipStream_t s);
 
+// Range search (kernels/range.hip): every (query row, gallery row) whose score -- launch_topk's score,
+// bit for bit -- is >= threshold as an f32 comparison (a NaN score never passes), appended to a bounded
+// record buffer in no particular order.  One launch: nq query rows (the wide kernel, or the few-query one
+// when plan.narrow) against columns [col0, N) cut into plan.n_spans spans of plan.span_cols columns
+// (col0 % 64 == 0; the plan is topk_plan(N - col0, nq, ...)).  A hit at position p of the counter's order
+// writes out_query[p] = q_off + its query row, out_row[p] = its column, out_score[p] = its score, if
+// p < capacity; *total (8-byte aligned, zeroed by the caller before the first launch that adds to it)
+// counts every hit, past the capacity too.  mask as in TopkArgs.
+// join: the query rows are the gallery rows q_off .. q_off + nq themselves (q = those rows as f32), and a
+// column j passes for query row i = q_off + r only if j > i and row i is allowed by mask as well; col0 is
+// then q_off & ~63, so that no column below it is visited.
+constexpr long kRangeMaxRecords = 1L << 28;
+struct RangeArgs {
+  const float* q;  // [nq][E]
+  int nq;
+  const void* g;  // [N][E] of dtype (TopkGal)
+  int dtype, N, E;
+  float scale, bias, threshold;
+  TopkPlan plan;
+  unsigned col0;
+  const uint32_t* mask;
+  int q_off;
+  bool join;
+  long capacity;  // 1 .. kRangeMaxRecords
+  int32_t* out_query;
+  int32_t* out_row;
+  float* out_score;
+  unsigned long long* total;
+  hipStream_t stream;
+};
+hipError_t launch_range(const RangeArgs& a);
+
 // The gallery's storage conversion (kernels/gallery.hip).  Bytes of one element:
 int topk_gal_bytes(int dtype);
 // f32 -> f16 / bf16 rows, round to nearest even (f16: subnormals kept, |x| >= 65520 -> inf; NaN stays

@@ -46,6 +46,7 @@
 #include "gallery.hpp"
 #include "kernels.hpp"
 #include "topk_key.hpp"
+#include "topk_stage.hpp"
 
 namespace clipgpu {
 
@@ -54,8 +55,7 @@ std::atomic<int> g_topk_route{0};
 
 namespace {
 
-constexpr int TB = 64, TK = 64;
-constexpr int KQ = 20, LDT = 88;  // staged row: 4 k slots of 16 steps + 4, + 8: conflict-free 16-byte reads
+// (TB, TK, KQ, LDT, NB, the staging layout and the gallery element as loaded: topk_stage.hpp)
 constexpr int CAND1 = 32;  // phase 1 candidate slots per row (one ballot adds at most 16 to a row)
 constexpr int CAND2 = 64;  // phase 2 (one ballot adds at most 64)
 #ifndef CLIPGPU_TOPK_MERGE_STEPS
@@ -65,25 +65,6 @@ constexpr int CAND2 = 64;  // phase 2 (one ballot adds at most 64)
 // A selection entry: x = the score's own f32 bits, y = gallery index.  Compared by topk_key.
 __device__ __forceinline__ uint64_t ent_key(uint2 e) { return topk_key(e.x, e.y); }
 __device__ __forceinline__ uint2 ent_empty() { return make_uint2(kTopkEmptyScore, kTopkEmptyIndex); }
-
-// LDS traffic of one wave is processed in program order; this keeps the compiler from moving it.
-__device__ __forceinline__ void wave_lds_order() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// The same elements as loaded (held in registers while the loads are in flight) and widened when staged.
-template <typename GT> struct GalRaw { typedef uint2 type; };
-template <> struct GalRaw<float> { typedef float4 type; };
-__device__ __forceinline__ float4 gal_raw(const float* p) { return *(const float4*)p; }
-__device__ __forceinline__ uint2 gal_raw(const _Float16* p) { return *(const uint2*)p; }
-__device__ __forceinline__ uint2 gal_raw(const __bf16* p) { return *(const uint2*)p; }
-template <typename GT> __device__ __forceinline__ float4 gal_widen(float4 v) { return v; }
-template <typename GT> __device__ __forceinline__ float4 gal_widen(uint2 u) {
-  union { uint2 u; GT h[4]; } x;
-  x.u = u;
-  return gal4(x.h);
-}
 
 // Wave-cooperative (all 64 lanes, uniform arguments).  ent[0 .. k) is the row's current best list,
 // ent[k .. k + c) its candidates (k + c <= 192).  Leaves the k best of both in ent[0 .. k), best
@@ -416,8 +397,6 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(const uint2* __restrict
 // the word arrives with the tile's last slab and the selection starts no load of its own.  A tile is
 // never skipped -- a conditional request would end the counting of the loads in flight; only a span
 // with no allowed row leaves at once.
-constexpr int NB = 16;
-
 //
 // PROBS: as in the wide kernel; the columns of the step past the span are all >= c_end and are not counted.
 template <int KC, typename GT, bool MASKED, bool PROBS>

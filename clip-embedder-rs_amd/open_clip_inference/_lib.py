@@ -79,6 +79,12 @@ _PROTOS = [
                                            c_void_p, c_void_p, c_void_p, c_void_p]),
     ("clipgpu_index_search_probs_device", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_int,
                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("clipgpu_index_range_search_device", c_int, [c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_void_p,
+                                                  c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("clipgpu_index_range_search", c_int, [c_void_p, c_void_p, c_int64, c_float, c_float, c_float, c_void_p, c_int64,
+                                           c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("clipgpu_index_self_join", c_int, [c_void_p, c_float, c_float, c_float, c_void_p, c_int64, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]),
     ("clipgpu_comm_unique_id", c_int, [c_void_p]),
     ("clipgpu_comm_init_rank", c_int, [c_void_p, c_void_p, c_int, c_int]),
     ("clipgpu_comm_info", c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),

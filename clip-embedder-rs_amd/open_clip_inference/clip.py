@@ -144,6 +144,25 @@ class Clip:
         idx, score = index.search(self.text.embed_texts(texts), k, float(scale), float(bias), allow=allow)
         return [[(int(i), float(s)) for i, s in zip(ri, rs) if i >= 0] for ri, rs in zip(idx, score)]
 
+    def search_above(self, index, texts: Sequence[str], min_logit: float, allow=None, max_results: int = 1 << 20
+                     ) -> List[List[Tuple[int, float]]]:
+        """``search`` by score instead of by count: per text EVERY row of ``index`` whose logit (the model's
+        logit_scale / logit_bias, as ``search``) is >= ``min_logit``, as (gallery index, logit), best first.
+        ``allow`` as in ``search``; more than ``max_results`` results in all raise ``ResultOverflow``
+        (``EmbeddingIndex.range_search``)."""
+        scale, bias = self._scale_bias()
+        lims, idx, score = index.range_search(self.text.embed_texts(texts), min_logit, float(scale), float(bias),
+                                              allow=allow, max_results=max_results)
+        return [[(int(i), float(s)) for i, s in zip(idx[a:b], score[a:b])] for a, b in zip(lims[:-1], lims[1:])]
+
+    def find_duplicates(self, index, min_cosine: float, allow=None, max_pairs: int = 1 << 20
+                        ) -> List[Tuple[int, int, float]]:
+        """Near-duplicates in a gallery: every pair i < j of live (and allowed) rows of ``index`` whose cosine
+        (the rows are L2-normalised embeddings; scale 1, bias 0) is >= ``min_cosine``, as (i, j, cosine)
+        sorted by (i, j) (``EmbeddingIndex.duplicates``)."""
+        pairs, score = index.duplicates(min_cosine, 1.0, 0.0, allow=allow, max_pairs=max_pairs)
+        return [(int(i), int(j), float(s)) for (i, j), s in zip(pairs, score)]
+
     def rank(self, index, texts: Sequence[str], k: int, allow=None) -> List[List[Tuple[int, float]]]:
         """rank_images (src/clip.rs:134-170) against a resident gallery, cut to its k best: per text
         [(gallery index, probability)], best first, with the model's activation (softmax over all live

@@ -22,6 +22,15 @@ class InferenceError(ClipError):
     """``ClipError::Inference`` (e.g. "Empty batch", src/vision.rs:121-123)"""
 
 
+class ResultOverflow(InferenceError):
+    """``EmbeddingIndex.range_search`` / ``duplicates`` found more results than ``max_results`` /
+    ``max_pairs`` allowed; ``needed`` is the exact total, the size to retry with."""
+
+    def __init__(self, msg: str, needed: int):
+        super().__init__(msg)
+        self.needed = int(needed)
+
+
 class ShapeError(ClipError):
     """``ClipError::Shape``"""
 

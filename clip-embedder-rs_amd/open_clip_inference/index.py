@@ -13,6 +13,7 @@ import numpy as np
 from ._lib import check, lib
 
 TOPK_MAX = 128  # CLIPGPU_TOPK_MAX
+RANGE_MAX = 1 << 28  # most records of a range search or a self-join (include/clipgpu.h)
 DTYPES = {"f32": 0, "f16": 1, "bf16": 2}  # enum clipgpu_index_dtype
 PROB_ACTIVATIONS = {"softmax": 0, "sigmoid": 1}  # CLIPGPU_SIM_SOFTMAX, CLIPGPU_SIM_SIGMOID
 
@@ -41,7 +42,9 @@ class EmbeddingIndex:
     of the rounded rows returns (include/clipgpu.h has the bound on a logit's change).  ``remove``
     marks rows dead without moving the others, ``set_rows`` overwrites rows in place (and revives
     them), and ``search(..., allow=)`` searches a subset, exactly.  ``search_probs`` is the same search
-    with the softmax (over all searched rows) or sigmoid probabilities of the k results."""
+    with the softmax (over all searched rows) or sigmoid probabilities of the k results.  ``range_search``
+    returns every row at or above a score threshold instead of the k best, and ``duplicates`` joins the
+    gallery against itself at a threshold; neither builds the score matrix."""
 
     def __init__(self, E: int, capacity: int, device: int = 0, dtype: str = "f32"):
         self._h = None
@@ -187,6 +190,83 @@ class EmbeddingIndex:
                                                          float(logit_scale), float(logit_bias),
                                                          c_void_p(d_allow or None), c_void_p(d_idx), c_void_p(d_score),
                                                          c_void_p(stream or None)))
+
+    @staticmethod
+    def _range_args(threshold, limit, what: str) -> Tuple[float, int]:
+        """(threshold, the result limit), checked before any native call."""
+        thr = float(threshold)
+        if thr != thr:
+            raise ValueError("threshold must not be NaN")
+        if isinstance(limit, bool) or not isinstance(limit, (int, np.integer)):
+            raise TypeError(f"{what} must be an integer, got {type(limit).__name__}")
+        if not 1 <= int(limit) <= RANGE_MAX:
+            raise ValueError(f"{what} must be in 1..{RANGE_MAX} (2^28), got {int(limit)}")
+        return thr, int(limit)
+
+    @staticmethod
+    def _check_range(rc: int, total: int, limit: int, what: str) -> None:
+        """``check`` for the range forms: an overflow becomes ``ResultOverflow`` with the needed size."""
+        if rc != 0 and total > limit:
+            from .error import ResultOverflow
+            msg = lib().clipgpu_last_error().decode("utf-8", "replace")
+            raise ResultOverflow(f"{msg}: pass {what}={total}", total)
+        check(rc)
+
+    def range_search(self, queries, threshold: float, logit_scale: float = 1.0, logit_bias: float = 0.0, allow=None,
+                     max_results: int = 1 << 20) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """EVERY live (and allowed) row whose score is >= ``threshold``, per query, for a caller who knows a
+        score and not a k: (lims int64 [nq + 1], idx int64 [total], scores f32 [total]); query q's rows are
+        ``idx[lims[q]:lims[q + 1]]``, best first, in ``search``'s order and with ``search``'s scores, bit for
+        bit.  The comparison is f32 ``score >= threshold``; a NaN score never passes.  ``max_results``
+        bounds the device buffer the results pass through (12 bytes each); more results than that raise
+        ``ResultOverflow``, whose ``needed`` is the exact total to retry with."""
+        thr, cap = self._range_args(threshold, max_results, "max_results")
+        words = self._allow_words(allow)
+        q = self._rows(queries, "queries")
+        lims = np.zeros(q.shape[0] + 1, np.int64)
+        idx = np.empty(cap, np.int64)
+        score = np.empty(cap, np.float32)
+        total = ctypes.c_int64(-1)
+        rc = lib().clipgpu_index_range_search(self.handle, q.ctypes.data, q.shape[0], thr, float(logit_scale),
+                                              float(logit_bias), None if words is None else words.ctypes.data, cap,
+                                              lims.ctypes.data, idx.ctypes.data, score.ctypes.data,
+                                              ctypes.addressof(total))
+        self._check_range(rc, total.value, cap, "max_results")
+        return lims, idx[:total.value].copy(), score[:total.value].copy()
+
+    def range_search_device(self, d_queries: int, nq: int, threshold: float, capacity: int, d_out_query: int,
+                            d_out_row: int, d_out_score: int, d_out_total: int, logit_scale: float = 1.0,
+                            logit_bias: float = 0.0, stream: int = 0, d_allow: int = 0) -> None:
+        """``range_search`` on device pointers, unsorted: records (query int32, row int32, score f32) go to
+        three device arrays of ``capacity`` entries in no particular order, and the uint64 at ``d_out_total``
+        (8-byte aligned; zeroed by this call on ``stream``) counts every hit, past the capacity too --
+        min(total, capacity) records are valid, the complete set if total <= capacity.  Ordered on ``stream``;
+        returns without synchronising."""
+        thr, cap = self._range_args(threshold, capacity, "capacity")
+        check(lib().clipgpu_index_range_search_device(self.handle, c_void_p(d_queries), int(nq), thr,
+                                                      float(logit_scale), float(logit_bias), c_void_p(d_allow or None),
+                                                      cap, c_void_p(d_out_query), c_void_p(d_out_row),
+                                                      c_void_p(d_out_score), c_void_p(d_out_total),
+                                                      c_void_p(stream or None)))
+
+    def duplicates(self, threshold: float, logit_scale: float = 1.0, logit_bias: float = 0.0, allow=None,
+                   max_pairs: int = 1 << 20) -> Tuple[np.ndarray, np.ndarray]:
+        """The gallery joined against itself: every pair i < j of live (and allowed) rows with
+        score(i, j) >= ``threshold``, as (pairs int64 [n, 2] sorted by (i, j), scores f32 [n]).  With the
+        default scale 1 and bias 0 on unit rows the threshold is a cosine.  A score is exactly
+        ``similarity(rows(), rows())[i, j]``.  Overflow as in ``range_search``."""
+        thr, cap = self._range_args(threshold, max_pairs, "max_pairs")
+        words = self._allow_words(allow)
+        oi = np.empty(cap, np.int64)
+        oj = np.empty(cap, np.int64)
+        score = np.empty(cap, np.float32)
+        total = ctypes.c_int64(-1)
+        rc = lib().clipgpu_index_self_join(self.handle, thr, float(logit_scale), float(logit_bias),
+                                           None if words is None else words.ctypes.data, cap, oi.ctypes.data,
+                                           oj.ctypes.data, score.ctypes.data, ctypes.addressof(total))
+        self._check_range(rc, total.value, cap, "max_pairs")
+        n = total.value
+        return np.stack([oi[:n], oj[:n]], axis=1), score[:n].copy()
 
     @staticmethod
     def _prob_args(k, activation) -> Tuple[int, int]:

@@ -355,7 +355,36 @@ int clipgpu_similarity_device(const float* d_img, int64_t n_img, const float* d_
  * A NaN or +inf logit in A makes every softmax probability of that query NaN, as the reference's
  * exp(x - max) does; -inf logits add nothing (all of A at -inf: NaN, as there).  Mutex, event ordering,
  * chunking, host staging and "the _device form does not synchronise" are those of the other searches;
- * the pairs (at most 512 KiB) and the staged outputs are part of the work area allocated at creation. */
+ * the pairs (at most 512 KiB) and the staged outputs are part of the work area allocated at creation.
+ *
+ * Range search and duplicate pairs.  clipgpu_index_range_search[_device] return EVERY live allowed row whose
+ * score against a query is >= threshold (an f32 comparison of the score above, bit-identical to the search's
+ * and to clipgpu_similarity's logits; a NaN score never passes, not even at threshold = -inf), for callers
+ * who know a score and not a k.  `allow` / `d_allow` as in the filtered search.
+ *   _device form: records (query index, gallery row, score) go to d_out_query / d_out_row / d_out_score
+ *     (device arrays of `capacity` entries each, 12 bytes per record together) in NO particular order, and
+ *     *d_out_total (device, 8-byte aligned; zeroed by the call on `stream`) counts every hit, past the
+ *     capacity too.  Once `stream` has run, min(total, capacity) records are valid; if total <= capacity they
+ *     are the complete set.  No record is ever written at or past `capacity`.  Ordered after the handle's last
+ *     operation; does not synchronise.
+ *   host form: CSR.  out_lims [nq + 1]; query q's results are out_idx / out_score [out_lims[q], out_lims[q+1])
+ *     in the search's order (descending score, equal scores by ascending row); out_idx and out_score have
+ *     max_results entries.  *out_total is written whenever the device work ran.  total > max_results is
+ *     CLIPGPU_ERR_INVALID with a message that names both numbers; the output arrays are then unspecified and
+ *     the caller retries with max_results >= *out_total.  The records pass through a device buffer of
+ *     max_results * 12 bytes that the handle allocates at the first such call, grows when a later call asks
+ *     for more and keeps until it is destroyed (a failed allocation is CLIPGPU_ERR_DEVICE and leaves the
+ *     index usable), and through twice those bytes of host memory for the sort.
+ *   clipgpu_index_self_join: the gallery against itself, every pair i < j of live allowed rows with
+ *     score(i, j) >= threshold, sorted by (i, j) ascending, out_i / out_j / out_score [max_pairs]; overflow,
+ *     *out_total and the record buffer as in the host form above.  Rows i are read as stored (a 16-bit
+ *     gallery: widened, exactly), so (i, j) carries exactly clipgpu_similarity(rows, rows)[i][j] of the
+ *     stored rows -- the product chain does not care which side is which, the score is symmetric bit for bit.
+ *     With logit_scale 1 and logit_bias 0 on L2-normalised rows the threshold is a cosine.
+ * Limits, refused with CLIPGPU_ERR_INVALID before any device call: a NULL handle or output, nq <= 0 or an
+ * empty index ("Empty batch"), nq > 2^31 - 1 (a record holds an int32 query index), a NaN threshold, and
+ * capacity / max_results / max_pairs outside 1 .. 2^28 (2^28 records are 3 GiB of device memory and, for
+ * the host forms, twice that in host memory while they sort). */
 typedef struct clipgpu_index clipgpu_index;
 #define CLIPGPU_TOPK_MAX 128
 enum clipgpu_index_dtype { CLIPGPU_INDEX_F32 = 0, CLIPGPU_INDEX_F16 = 1, CLIPGPU_INDEX_BF16 = 2 };
@@ -387,6 +416,16 @@ int clipgpu_index_search_probs(clipgpu_index* ix, const float* queries, int64_t 
 int clipgpu_index_search_probs_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k,
                                       float logit_scale, float logit_bias, int activation, const uint32_t* d_allow,
                                       int64_t* d_idx, float* d_score, float* d_prob, float* d_norm, void* stream);
+int clipgpu_index_range_search_device(clipgpu_index* ix, const float* d_queries, int64_t nq, float threshold,
+                                      float logit_scale, float logit_bias, const uint32_t* d_allow, int64_t capacity,
+                                      int32_t* d_out_query, int32_t* d_out_row, float* d_out_score,
+                                      uint64_t* d_out_total, void* stream);
+int clipgpu_index_range_search(clipgpu_index* ix, const float* queries, int64_t nq, float threshold, float logit_scale,
+                               float logit_bias, const uint32_t* allow, int64_t max_results, int64_t* out_lims,
+                               int64_t* out_idx, float* out_score, int64_t* out_total);
+int clipgpu_index_self_join(clipgpu_index* ix, float threshold, float logit_scale, float logit_bias,
+                            const uint32_t* allow, int64_t max_pairs, int64_t* out_i, int64_t* out_j, float* out_score,
+                            int64_t* out_total);
 
 /* ---- data-parallel sharding + the RCCL all-gather (north_star: "batches shard
  * data-parallel across the 8 GPUs of one node with an RCCL all-gather over xGMI only for the final

@@ -257,6 +257,104 @@ def topk_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 4, 16, 17, 32, 256
         _lib.check(L.clipgpu_test_topk_route(0))
 
 
+def topk_range_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 16, 256), dtypes=("f32", "f16"), NJ=1 << 17,
+                   min_cosine=0.2):
+    """The range search against the search it shares its hot loop with, per query count and storage type:
+    legs alternating in one process (rotating order, device-event timings after `warmup` rounds) --
+    range_search_device at a threshold that about k rows per query pass (the median over the queries of the
+    k-th score of a search), search_device(k) on the same inputs (the yardstick), and at Q = 16 also
+    range_search_device at threshold -inf into a small buffer: every column a hit, the cost of dense
+    emission (one counter add per wave and tile; nearly every record is dropped at the capacity).  The
+    range leg's total is checked against the scores of a k = 128 search.  Then the self-join of NJ rows
+    (EmbeddingIndex.duplicates at `min_cosine`, host form: launches, copy-back and host sort included, wall
+    clock) against what a user does today, search_device of every row with k = 128 (wall clock to the end
+    of the device work, without reading the result back or pairing it up)."""
+    from open_clip_inference import EmbeddingIndex
+    torch.manual_seed(0)
+    s = torch.cuda.current_stream().cuda_stream
+    g = torch.nn.functional.normalize(torch.randn(N, E, device="cuda"), dim=1)
+    qs = {Q: torch.nn.functional.normalize(torch.randn(Q, E, device="cuda"), dim=1) for Q in Qs}
+    for dt in dtypes:
+        esz, _ = INDEX_DTYPES[dt]
+        with EmbeddingIndex(E, N, dtype=dt) as ix:
+            ix.add_device(g.data_ptr(), N, s)
+            for Q in Qs:
+                q = qs[Q]
+                idx128 = torch.empty((Q, 128), dtype=torch.int64, device="cuda")
+                sc128 = torch.empty((Q, 128), device="cuda")
+                ix.search_device(q.data_ptr(), Q, 128, idx128.data_ptr(), sc128.data_ptr(), 100.0, 0.0, s)
+                thr = float(sc128[:, k - 1].median())
+                expect = int((sc128 >= thr).sum())
+                assert int((sc128[:, -1] >= thr).sum()) == 0  # 128 were enough to count the hits
+                cap = 64 * Q + 1024
+                rec = (torch.empty(cap, dtype=torch.int32, device="cuda"), torch.empty(cap, dtype=torch.int32, device="cuda"),
+                       torch.empty(cap, device="cuda"))
+                tot = {name: torch.zeros(1, dtype=torch.int64, device="cuda") for name in ("range", "dense")}
+                idx, sc = torch.empty((Q, k), dtype=torch.int64, device="cuda"), torch.empty((Q, k), device="cuda")
+
+                def ranged(name, t):
+                    ix.range_search_device(q.data_ptr(), Q, t, cap, rec[0].data_ptr(), rec[1].data_ptr(), rec[2].data_ptr(),
+                                           tot[name].data_ptr(), 100.0, 0.0, s)
+
+                legs = [("range", lambda: ranged("range", thr)),
+                        ("search", lambda: ix.search_device(q.data_ptr(), Q, k, idx.data_ptr(), sc.data_ptr(), 100.0, 0.0, s))]
+                if Q == 16:
+                    legs.append(("dense", lambda: ranged("dense", float("-inf"))))
+                ms = {name: [] for name, _ in legs}
+                for rnd in range(warmup + runs):
+                    r = rnd % len(legs)
+                    for name, fn in legs[r:] + legs[:r]:  # every leg follows every other equally often
+                        t = _event_ms(fn)
+                        if rnd >= warmup:
+                            ms[name].append(t)
+                assert int(tot["range"]) == expect, (int(tot["range"]), expect)
+                nbytes = N * E * esz
+                out = {"measure": "topk_range", "Q": Q, "dtype": dt, "N": N, "E": E, "k": k, "runs": runs,
+                       "threshold": round(thr, 4), "hits": expect, "same_count_as_search": True}
+                for name, v in ms.items():
+                    out[name] = _stats(v, nbytes)
+                out["range_over_search"] = round(out["range"]["ms_median"] / out["search"]["ms_median"], 3)
+                if Q == 16:
+                    assert int(tot["dense"]) == Q * N
+                    out["dense_hits"], out["dense_capacity"] = Q * N, cap
+                print(json.dumps(out), flush=True)
+    # the self-join: NJ rows of the same gallery, f32
+    gj = g[:NJ].contiguous()
+    with EmbeddingIndex(E, NJ) as ix:
+        ix.add_device(gj.data_ptr(), NJ, s)
+        idx128 = torch.empty((NJ, 128), dtype=torch.int64, device="cuda")
+        sc128 = torch.empty((NJ, 128), device="cuda")
+        found = {}
+
+        def join():
+            found["pairs"], found["cos"] = ix.duplicates(min_cosine, max_pairs=1 << 22)
+
+        def every_row():
+            ix.search_device(gj.data_ptr(), NJ, 128, idx128.data_ptr(), sc128.data_ptr(), 1.0, 0.0, s)
+            torch.cuda.synchronize()
+
+        ms = {"self_join": [], "search_every_row_k128": []}
+        for rnd in range(warmup + runs):
+            for name, fn in (("self_join", join), ("search_every_row_k128", every_row)):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                fn()
+                if rnd >= warmup:
+                    ms[name].append((time.perf_counter() - t0) * 1e3)
+        # the same pairs: every result of the k = 128 searches above the cut, j > i, is a pair of the join
+        hit = (sc128 >= min_cosine) & (idx128 > torch.arange(NJ, device="cuda")[:, None])
+        assert int((sc128[:, -1] >= min_cosine).sum()) == 0 and int(hit.sum()) == len(found["pairs"])
+        out = {"measure": "self_join", "N": NJ, "E": E, "dtype": "f32", "min_cosine": min_cosine, "runs": runs,
+               "pairs": len(found["pairs"]), "same_pairs_as_search": True}
+        for name, v in ms.items():
+            med = float(np.median(v))
+            out[name] = {"ms_median": round(med, 2), "ms_min_max": [round(min(v), 2), round(max(v), 2)]}
+        med = out["self_join"]["ms_median"]
+        out["tflops_f32_of_N2E"] = round(2.0 * NJ * NJ * E / (med * 1e-3) / 1e12, 1)  # the full square's FLOP / time
+        out["derived_ms_at_N_2^20"] = round(med * (float(1 << 20) / NJ) ** 2, 0)
+        print(json.dumps(out), flush=True)
+
+
 def topk_routes_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 2, 4, 8, 12, 16)):
     """The measurement kNarrowRows (csrc/kernels/kernels.hpp) is set by: for every query count the
     few-query kernel can take, that kernel (route 2) against the wide one (route 1) on an f32 gallery,
@@ -483,6 +581,8 @@ if __name__ == "__main__":
         topk_filter_leg()
     if "topkprobs" in which:  # the probability search against the plain search and the matrix softmax + topk
         topk_probs_leg()
+    if "topkrange" in which:  # the range search against search k = 10, dense emission, and the self-join
+        topk_range_leg()
     if "so400m" in which:
         device_leg("so400m_vision", SO400M_16_SIGLIP2_384_CFG, 0, 128)
     if "h14" in which:
