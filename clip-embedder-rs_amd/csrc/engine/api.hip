@@ -268,7 +268,8 @@ int clipgpu_embed_u8_device(clipgpu_engine* e, const uint8_t* d_nhwc, int64_t B,
 static void check_similarity_args(int64_t n_img, int64_t n_txt, int64_t E, int activation, int axis) {
   if (n_img <= 0 || n_txt <= 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
   if (E <= 0 || E % 16) throw ClipErr(CLIPGPU_ERR_INVALID, "Shape error: embedding dim must be a multiple of 16");
-  if (n_img > (1L << 22) || n_txt > (1L << 30) || n_img * n_txt > (1L << 40))
+  // 65535 * 64: launch_similarity's grid has one y block per 64 image rows
+  if (n_img > 65535L * 64 || n_txt > (1L << 30) || n_img * n_txt > (1L << 40))
     throw ClipErr(CLIPGPU_ERR_INVALID, "Shape error: similarity matrix too large");
   if (activation < CLIPGPU_SIM_SOFTMAX || activation > CLIPGPU_SIM_LOGITS || axis < 0 || axis > 1)
     throw ClipErr(CLIPGPU_ERR_INVALID, "bad activation / axis");

@@ -10,7 +10,7 @@
 // accumulate; the 1/16-rate f32 matrix path, still ~10x the VALU FMA loop), 64 x 64 output
 // tiles per 4-wave block, K staged through LDS 16 at a time.  The logit is one fmaf (Rust
 // f32::mul_add); exp / divide are IEEE (expf, '/').  Embeddings are [n][E] row-major f32,
-// E % 4 == 0.
+// E % 16 == 0.
 #include "common.hpp"
 #include "kernels.hpp"
 

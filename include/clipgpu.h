@@ -247,7 +247,9 @@ int64_t clipgpu_tokenizer_vocab_size(const clipgpu_tokenizer* t);
  *     of each image (classify, :92-132), 0 = over the images of each label (rank_images,
  *     :134-170);  CLIPGPU_SIM_SIGMOID: elementwise sigmoid (activation_function "sigmoid");
  *   CLIPGPU_SIM_LOGITS: the logits themselves (compare, :79-90).
- * img [n_img][E], txt [n_txt][E] f32 (the embed_* outputs); out [n_img][n_txt] f32; E % 16 == 0.
+ * img [n_img][E], txt [n_txt][E] f32 (the embed_* outputs); out [n_img][n_txt] f32; E % 16 == 0,
+ * n_img <= 65535 * 64 = 4194240, n_txt <= 2^30, n_img * n_txt <= 2^40 (anything else: CLIPGPU_ERR_INVALID,
+ * "Shape error: ...").
  * Host-buffer form on GPU `device`; the _device form takes device pointers and a stream.
  * (The descending sort of classify / rank_images stays on the host.) */
 enum clipgpu_sim_activation { CLIPGPU_SIM_SOFTMAX = 0, CLIPGPU_SIM_SIGMOID = 1, CLIPGPU_SIM_LOGITS = 2 };
