@@ -26,9 +26,15 @@
 // bounded record buffer behind one 64-bit counter.  The device form writes the caller's buffers; the host forms
 // use a record buffer of the handle's (allocated at the first such call, grown on demand), sort the records on
 // the host and refuse an overflow with the exact total.
+//
+// Assignment and k-means (clipgpu_index_assign[_device], clipgpu_index_kmeans; kernels/cluster.hip).  One launch
+// assigns every slot under the search's mask; there is no span cut and no chunking, a block owns 64 gallery
+// rows.  k-means alternates that launch with an integer-sum update and reads one counter back per iteration;
+// its labels, scores, centroids and sums live in buffers of the handle's, lazy like the record buffer.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <mutex>
 #include <string>
@@ -75,6 +81,15 @@ struct clipgpu_index {
   size_t scratch_bytes = 0;
   char* res = nullptr;           // range search / self-join, host forms: the counter and res_records records; lazy
   int64_t res_records = 0;
+  // assign (host form) and kmeans; lazy, grown on demand, carved by cluster_buffers:
+  char* cl_rows = nullptr;       // a ClusterStat, two generations of int32 labels and the scores, cl_rows_n rows each
+  int64_t cl_rows_n = 0;
+  char* cl_cen = nullptr;        // the centroids f32 [cl_cen_n][E]
+  int64_t cl_cen_n = 0;
+  char* cl_sum = nullptr;        // kmeans: the sums int64 [cl_sum_n][E]
+  int64_t cl_sum_n = 0;
+  int64_t km_C = 0;              // the last update's centroid count (0 = none yet) and shift, for
+  int km_shift = 0;              // clipgpu_test_index_kmeans_sums
   hipStream_t stream = nullptr;  // the host-buffer forms' stream
   hipEvent_t done = nullptr;     // recorded after every device-side operation
 };
@@ -353,6 +368,66 @@ std::vector<RangeRec> fetch_records(clipgpu_index* ix, const RangeBuf& b, int64_
   return rec;
 }
 
+// ---- assignment and k-means (kernels/cluster.hip) --------------------------------------------------------
+// A device buffer of the handle's for `need` entries of `bytes` in all: allocated at the first use, grown when
+// a call needs more, freed with the handle.  A failed allocation is CLIPGPU_ERR_DEVICE and leaves the handle
+// without the buffer, usable.  Callers hold the mutex and have waited for `done`.
+void grow(char*& p, int64_t& have, int64_t need, size_t bytes) {
+  if (need <= have) return;
+  if (p) HIP_CHECK(hipFree(p));
+  p = nullptr;
+  have = 0;
+  HIP_CHECK(hipMalloc((void**)&p, bytes));
+  have = need;
+}
+
+struct ClusterBuf { ClusterStat* stat; int32_t* label[2]; float* score; float* cen; int64_t* sum; };
+
+// The buffers of a host assign (sums = false) or a kmeans over the present rows and C centroids.
+ClusterBuf cluster_buffers(clipgpu_index* ix, int64_t C, bool sums) {
+  grow(ix->cl_rows, ix->cl_rows_n, ix->size, 256 + 3 * align256((size_t)ix->size * 4));
+  grow(ix->cl_cen, ix->cl_cen_n, C, (size_t)C * ix->E * 4);
+  if (sums && C > ix->cl_sum_n) {
+    ix->km_C = 0;  // the sums of the last update go with the buffer
+    grow(ix->cl_sum, ix->cl_sum_n, C, (size_t)C * ix->E * 8);
+  }
+  size_t off = 0;
+  ClusterBuf b;
+  b.stat = carve<ClusterStat>(ix->cl_rows, off, sizeof(ClusterStat));
+  for (int g = 0; g < 2; ++g) b.label[g] = carve<int32_t>(ix->cl_rows, off, (size_t)ix->cl_rows_n * 4);
+  b.score = carve<float>(ix->cl_rows, off, (size_t)ix->cl_rows_n * 4);
+  b.cen = (float*)ix->cl_cen;
+  b.sum = (int64_t*)ix->cl_sum;
+  return b;
+}
+
+// The refusals that need no lock and no device; then as enter_search.
+std::unique_lock<std::mutex> enter_cluster(clipgpu_index* ix, bool null_arg, int64_t C) {
+  if (!ix || null_arg) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+  if (C < 1 || C > kClusterMaxCentroids)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "the number of centroids must be in 1.." + std::to_string(kClusterMaxCentroids) +
+                                           ", got " + std::to_string(C));
+  std::unique_lock<std::mutex> lk(ix->mu);
+  if (ix->size == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");  // an empty gallery
+  HIP_CHECK(hipSetDevice(ix->device));
+  return lk;
+}
+
+void assign_on(clipgpu_index* ix, const float* d_cen, int64_t C, float scale, float bias, const uint32_t* mask,
+               int32_t* d_label, float* d_score, hipStream_t s) {
+  HIP_CHECK(launch_assign({ix->gallery, ix->dtype, (int)ix->size, (int)ix->E, d_cen, (int)C, scale, bias, mask, d_label,
+                           d_score, s}));
+}
+
+// The labels (widened to int64) and scores of every slot, after the handle's stream has run.
+void fetch_assignment(clipgpu_index* ix, const int32_t* d_label, const float* d_score, int64_t* out_label,
+                      float* out_score) {
+  std::vector<int32_t> l((size_t)ix->size);
+  HIP_CHECK(copy_d2h(l.data(), d_label, l.size() * 4));
+  HIP_CHECK(copy_d2h(out_score, d_score, l.size() * 4));
+  for (size_t i = 0; i < l.size(); ++i) out_label[i] = l[i];
+}
+
 }  // namespace
 
 extern "C" {
@@ -489,6 +564,9 @@ void clipgpu_index_destroy(clipgpu_index* ix) {
   if (ix->stream) (void)hipStreamDestroy(ix->stream);
   if (ix->scratch) (void)hipFree(ix->scratch);
   if (ix->res) (void)hipFree(ix->res);
+  if (ix->cl_rows) (void)hipFree(ix->cl_rows);
+  if (ix->cl_cen) (void)hipFree(ix->cl_cen);
+  if (ix->cl_sum) (void)hipFree(ix->cl_sum);
   if (ix->work) (void)hipFree(ix->work);
   if (ix->gallery) (void)hipFree(ix->gallery);
   delete ix;
@@ -663,6 +741,149 @@ int clipgpu_index_search_device(clipgpu_index* ix, const float* d_queries, int64
 int clipgpu_index_search(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, float logit_scale,
                          float logit_bias, int64_t* out_idx, float* out_score) {
   return clipgpu_index_search_filtered(ix, queries, nq, k, logit_scale, logit_bias, nullptr, out_idx, out_score);
+}
+
+int clipgpu_index_get_rows_at(clipgpu_index* ix, const int64_t* ids, int64_t n, float* out_rows) {
+  return guarded([&]() {
+    check_ids(ix, ids, n);
+    if (!out_rows && n > 0) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    check_ids_in_range(ix, ids, n);
+    if (n == 0) return;
+    HIP_CHECK(hipSetDevice(ix->device));
+    HIP_CHECK(hipEventSynchronize(ix->done));
+    // the ids go to the device behind the f32 rows that the gather kernel widens into the scratch
+    for_each_piece(ix, n, 8, [&](int64_t r0, int64_t m, float* f32, void* d_ids) {
+      HIP_CHECK(copy_h2d(d_ids, ids + r0, (size_t)m * 8));
+      HIP_CHECK(launch_gal_gather(ix->dtype, ix->gallery, (const int64_t*)d_ids, f32, m, (int)ix->E, ix->stream));
+      HIP_CHECK(hipStreamSynchronize(ix->stream));
+      HIP_CHECK(copy_d2h(out_rows + r0 * ix->E, f32, (size_t)m * ix->E * 4));
+    });
+  });
+}
+
+int clipgpu_index_assign_device(clipgpu_index* ix, const float* d_centroids, int64_t C, float logit_scale,
+                                float logit_bias, const uint32_t* d_allow, int32_t* d_label, float* d_score,
+                                void* stream) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_cluster(ix, !d_centroids || !d_label || !d_score, C);
+    if ((uintptr_t)d_centroids & 15) throw ClipErr(CLIPGPU_ERR_INVALID, "d_centroids must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    order_after_last(ix, s);
+    assign_on(ix, d_centroids, C, logit_scale, logit_bias, build_mask(ix, d_allow, s), d_label, d_score, s);
+    mark_last(ix, s);
+  });
+}
+
+int clipgpu_index_assign(clipgpu_index* ix, const float* centroids, int64_t C, float logit_scale, float logit_bias,
+                         const uint32_t* allow, int64_t* out_label, float* out_score) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_cluster(ix, !centroids || !out_label || !out_score, C);
+    HIP_CHECK(hipEventSynchronize(ix->done));  // the filter area and the cluster buffers are free
+    const ClusterBuf b = cluster_buffers(ix, C, false);
+    if (allow) HIP_CHECK(copy_h2d(ix->d_eff, allow, (size_t)live_words(ix->size) * 4));
+    const uint32_t* mask = build_mask(ix, allow ? ix->d_eff : nullptr, ix->stream);
+    HIP_CHECK(copy_h2d(b.cen, centroids, (size_t)C * ix->E * 4));
+    assign_on(ix, b.cen, C, logit_scale, logit_bias, mask, b.label[0], b.score, ix->stream);
+    mark_last(ix, ix->stream);
+    HIP_CHECK(hipStreamSynchronize(ix->stream));
+    fetch_assignment(ix, b.label[0], b.score, out_label, out_score);
+  });
+}
+
+int clipgpu_index_kmeans(clipgpu_index* ix, int64_t C, float* centroids, int64_t max_iter, const uint32_t* allow,
+                         int64_t* out_label, float* out_score, int64_t* out_count, int64_t* out_moved,
+                         int64_t* out_iters) {
+  return guarded([&]() {
+    const bool null_arg = !centroids || !out_label || !out_score || !out_count || !out_moved || !out_iters;
+    if (!ix || null_arg) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+    if (max_iter < 1) throw ClipErr(CLIPGPU_ERR_INVALID, "max_iter must be at least 1, got " + std::to_string(max_iter));
+    const std::unique_lock<std::mutex> lk = enter_cluster(ix, false, C);  // held for the whole call
+    HIP_CHECK(hipEventSynchronize(ix->done));
+    const ClusterBuf b = cluster_buffers(ix, C, true);
+    hipStream_t s = ix->stream;
+    const int N = (int)ix->size, E = (int)ix->E;
+    if (allow) HIP_CHECK(copy_h2d(ix->d_eff, allow, (size_t)live_words(ix->size) * 4));
+    const uint32_t* mask = build_mask(ix, allow ? ix->d_eff : nullptr, s);
+    HIP_CHECK(copy_h2d(b.cen, centroids, (size_t)C * E * 4));
+    // the shift: m = the largest |x| of the live allowed rows, n = their number
+    ClusterStat st;
+    HIP_CHECK(hipMemsetAsync(b.stat, 0, sizeof(ClusterStat), s));
+    HIP_CHECK(launch_cluster_stats(ix->gallery, ix->dtype, N, E, mask, b.stat, s));
+    mark_last(ix, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    HIP_CHECK(copy_d2h(&st, b.stat, sizeof(st)));
+    if (st.bad_row)
+      throw ClipErr(CLIPGPU_ERR_INVALID, "row " + std::to_string(~st.bad_row) +
+                                             " has a non-finite element (k-means sums need finite rows)");
+    float m;
+    memcpy(&m, &st.max_bits, 4);
+    int e = 0, bits = 0;
+    if (m != 0.f) (void)std::frexp(m, &e);
+    for (unsigned n = st.n; n; n >>= 1) ++bits;
+    const int shift = 62 - e - bits;
+    // generation `cur` receives labels_t; labels_0 differs from every label and from -1
+    int cur = 0;
+    HIP_CHECK(hipMemsetAsync(b.label[1], 0xFE, (size_t)N * 4, s));
+    for (int64_t t = 0; t < max_iter; ++t) out_moved[t] = -1;
+    for (int64_t t = 1;; ++t) {
+      HIP_CHECK(hipMemsetAsync(&b.stat->moved, 0, 8, s));
+      assign_on(ix, b.cen, C, 1.f, 0.f, mask, b.label[cur], b.score, s);
+      HIP_CHECK(launch_cluster_moved(b.label[cur], b.label[cur ^ 1], N, &b.stat->moved, s));
+      mark_last(ix, s);
+      HIP_CHECK(hipStreamSynchronize(s));  // once per iteration
+      unsigned long long moved = 0;
+      HIP_CHECK(copy_d2h(&moved, &b.stat->moved, 8));
+      out_moved[t - 1] = (int64_t)moved;
+      *out_iters = t;
+      if (moved == 0) break;  // a fixed point: the centroids are not touched
+      HIP_CHECK(hipMemsetAsync(b.sum, 0, (size_t)C * E * 8, s));
+      HIP_CHECK(launch_cluster_sums(ix->gallery, ix->dtype, b.label[cur], N, E, shift, b.sum, s));
+      HIP_CHECK(launch_cluster_finalise(b.sum, (int)C, E, b.cen, s));
+      ix->km_C = C;
+      ix->km_shift = shift;
+      cur ^= 1;
+      if (t == max_iter) {  // unconverged: the labels and scores returned are those of the centroids returned
+        assign_on(ix, b.cen, C, 1.f, 0.f, mask, b.label[cur], b.score, s);
+        mark_last(ix, s);
+        HIP_CHECK(hipStreamSynchronize(s));
+        break;
+      }
+    }
+    fetch_assignment(ix, b.label[cur], b.score, out_label, out_score);
+    HIP_CHECK(copy_d2h(centroids, b.cen, (size_t)C * E * 4));
+    for (int64_t c = 0; c < C; ++c) out_count[c] = 0;
+    for (int64_t j = 0; j < ix->size; ++j)
+      if (out_label[j] >= 0) ++out_count[out_label[j]];
+  });
+}
+
+int clipgpu_test_index_kmeans_update(clipgpu_index* ix, const int32_t* d_label, int64_t C, int shift,
+                                     float* d_centroids, void* stream) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_cluster(ix, !d_label || !d_centroids, C);
+    HIP_CHECK(hipEventSynchronize(ix->done));
+    const ClusterBuf b = cluster_buffers(ix, C, true);
+    hipStream_t s = (hipStream_t)stream;
+    HIP_CHECK(hipMemsetAsync(b.sum, 0, (size_t)C * ix->E * 8, s));
+    HIP_CHECK(launch_cluster_sums(ix->gallery, ix->dtype, d_label, (int)ix->size, (int)ix->E, shift, b.sum, s));
+    HIP_CHECK(launch_cluster_finalise(b.sum, (int)C, (int)ix->E, d_centroids, s));
+    ix->km_C = C;
+    ix->km_shift = shift;
+    mark_last(ix, s);
+  });
+}
+
+int clipgpu_test_index_kmeans_sums(clipgpu_index* ix, int64_t C, int64_t* out_sums, int* out_shift) {
+  return guarded([&]() {
+    if (!ix || !out_sums || !out_shift) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (ix->km_C == 0 || C != ix->km_C) throw ClipErr(CLIPGPU_ERR_INVALID, "no k-means update with this many centroids has run");
+    HIP_CHECK(hipSetDevice(ix->device));
+    HIP_CHECK(hipEventSynchronize(ix->done));
+    HIP_CHECK(copy_d2h(out_sums, ix->cl_sum, (size_t)C * ix->E * 8));
+    *out_shift = ix->km_shift;
+  });
 }
 
 }  // extern "C"

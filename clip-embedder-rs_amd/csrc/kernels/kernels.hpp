@@ -279,6 +279,46 @@ struct RangeArgs {
 };
 hipError_t launch_range(const RangeArgs& a);
 
+// Assignment (kernels/cluster.hip): for every gallery row j < N the centroid with the largest
+// topk_key(score, centroid index), score = fmaf(dot(c, g[j]), scale, bias) with launch_topk's bits:
+// label[j] (int32) and score[j]; a row that mask (as in TopkArgs) does not allow gets (-1, -inf).  c: f32
+// [C][E], 16-byte aligned, 1 <= C <= kClusterMaxCentroids.  Nothing at or past N is written.
+constexpr int kClusterMaxCentroids = 65536;
+struct AssignArgs {
+  const void* g;  // [N][E] of dtype (TopkGal)
+  int dtype, N, E;
+  const float* c;
+  int C;
+  float scale, bias;
+  const uint32_t* mask;
+  int32_t* label;
+  float* score;
+  hipStream_t stream;
+};
+hipError_t launch_assign(const AssignArgs& a);
+// What a k-means call reads back from the device.  The launchers below add to it; the caller zeroes it.
+struct ClusterStat {
+  unsigned long long moved;  // launch_cluster_moved: rows with cur[i] >= 0 and cur[i] != prev[i]
+  unsigned max_bits;         // launch_cluster_stats: the largest |x| of the allowed rows, as f32 bits
+  unsigned bad_row;          // ~(the first allowed row with an inf or a NaN), 0 = none
+  unsigned n;                // the allowed rows
+  unsigned pad;
+};
+hipError_t launch_cluster_stats(const void* g, int dtype, int N, int E, const uint32_t* mask, ClusterStat* stat,
+                                hipStream_t s);
+hipError_t launch_cluster_moved(const int32_t* cur, const int32_t* prev, int N, unsigned long long* moved,
+                                hipStream_t s);
+// S[label[j]][i] += llrint(ldexp((double)g[j][i], shift)) for the rows with label[j] >= 0 (labels below the
+// row count of S [C][E], which the caller zeroes): 64-bit integer atomics, so the sums are exact and do not
+// depend on any order.  The caller picks the shift so that no sum reaches 2^62.
+hipError_t launch_cluster_sums(const void* g, int dtype, const int32_t* label, int N, int E, int shift, int64_t* S,
+                               hipStream_t s);
+// cen[c] = (float)(S[c] / sqrt(sum_i S[c][i]^2)) in f64, the sum sequential in i, without contraction; a row
+// of S that is all zeros leaves cen[c] as it is.
+hipError_t launch_cluster_finalise(const int64_t* S, int C, int E, float* cen, hipStream_t s);
+// out[i] (f32 [n][E]) = row ids[i] of the gallery, widened.  ids: device, inside the gallery.
+hipError_t launch_gal_gather(int dtype, const void* gal, const int64_t* ids, float* out, long n, int E, hipStream_t s);
+
 // The gallery's storage conversion (kernels/gallery.hip).  Bytes of one element:
 int topk_gal_bytes(int dtype);
 // f32 -> f16 / bf16 rows, round to nearest even (f16: subnormals kept, |x| >= 65520 -> inf; NaN stays

@@ -7,9 +7,9 @@ runs in ``lib/libclipgpu.so`` (hand-written gfx950 HIP kernels + C++ host runtim
 from .clip import Clip
 from .config import ModelConfig, OpenClipConfig
 from .error import ClipError, ResultOverflow
-from .index import EmbeddingIndex, pack_allow
+from .index import EmbeddingIndex, KMeansResult, pack_allow
 from .text import TextEmbedder
 from .vision import VisionEmbedder
 
-__all__ = ["Clip", "ClipError", "ResultOverflow", "EmbeddingIndex", "pack_allow", "TextEmbedder", "VisionEmbedder", "ModelConfig",
-           "OpenClipConfig"]
+__all__ = ["Clip", "ClipError", "ResultOverflow", "EmbeddingIndex", "KMeansResult", "pack_allow", "TextEmbedder",
+           "VisionEmbedder", "ModelConfig", "OpenClipConfig"]

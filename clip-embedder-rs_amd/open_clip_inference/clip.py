@@ -163,6 +163,15 @@ class Clip:
         pairs, score = index.duplicates(min_cosine, 1.0, 0.0, allow=allow, max_pairs=max_pairs)
         return [(int(i), int(j), float(s)) for (i, j), s in zip(pairs, score)]
 
+    def cluster(self, index, n_clusters: int, seed: int = 0, max_iter: int = 25, allow=None
+                ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Puts the live (and allowed) rows of ``index`` into ``n_clusters`` groups by cosine (spherical
+        k-means from ``n_clusters`` rows drawn with ``seed``; ``EmbeddingIndex.kmeans``): (labels int64
+        [len(index)], -1 for a row that is dead or not allowed; counts int64 [n_clusters]; centroids f32
+        [n_clusters, E], unit rows).  The same index, seed and arguments give the same bits on every run."""
+        km = index.kmeans(n_clusters, max_iter=max_iter, seed=seed, allow=allow)
+        return km.labels, km.counts, km.centroids
+
     def rank(self, index, texts: Sequence[str], k: int, allow=None) -> List[List[Tuple[int, float]]]:
         """rank_images (src/clip.rs:134-170) against a resident gallery, cut to its k best: per text
         [(gallery index, probability)], best first, with the model's activation (softmax over all live

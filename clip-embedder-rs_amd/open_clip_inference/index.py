@@ -6,7 +6,7 @@ from __future__ import annotations
 
 import ctypes
 from ctypes import c_void_p
-from typing import Tuple
+from typing import NamedTuple, Tuple
 
 import numpy as np
 
@@ -14,6 +14,7 @@ from ._lib import check, lib
 
 TOPK_MAX = 128  # CLIPGPU_TOPK_MAX
 RANGE_MAX = 1 << 28  # most records of a range search or a self-join (include/clipgpu.h)
+MAX_CENTROIDS = 1 << 16  # most centroids of assign and kmeans (include/clipgpu.h)
 DTYPES = {"f32": 0, "f16": 1, "bf16": 2}  # enum clipgpu_index_dtype
 PROB_ACTIVATIONS = {"softmax": 0, "sigmoid": 1}  # CLIPGPU_SIM_SOFTMAX, CLIPGPU_SIM_SIGMOID
 
@@ -31,6 +32,16 @@ def pack_allow(allowed) -> np.ndarray:
     return (bits.reshape(words, 32) << np.arange(32, dtype=np.uint64)).sum(axis=1, dtype=np.uint64).astype(np.uint32)
 
 
+class KMeansResult(NamedTuple):
+    """What ``EmbeddingIndex.kmeans`` returns."""
+    centroids: np.ndarray  # f32 [C, E]
+    labels: np.ndarray     # int64 [len(index)]: exactly assign(centroids); -1 for a dead or not allowed row
+    scores: np.ndarray     # f32 [len(index)]: the cosine to the row's centroid; -inf where the label is -1
+    counts: np.ndarray     # int64 [C]: the rows with each label
+    moved: np.ndarray      # int64 [iters]: per iteration, the rows whose label changed (the first: all of them)
+    iters: int             # assignments compared: <= max_iter; moved[-1] == 0 means converged
+
+
 class EmbeddingIndex:
     """``E``-dimensional rows (E % 16 == 0), at most ``capacity`` of them (fixed: the device
     memory is allocated here), on GPU ``device``.  Rows keep the order they were added in; a search
@@ -44,7 +55,8 @@ class EmbeddingIndex:
     them), and ``search(..., allow=)`` searches a subset, exactly.  ``search_probs`` is the same search
     with the softmax (over all searched rows) or sigmoid probabilities of the k results.  ``range_search``
     returns every row at or above a score threshold instead of the k best, and ``duplicates`` joins the
-    gallery against itself at a threshold; neither builds the score matrix."""
+    gallery against itself at a threshold; neither builds the score matrix.  ``assign`` gives every row its
+    nearest of C centroids and ``kmeans`` puts the rows into groups, reproducibly."""
 
     def __init__(self, E: int, capacity: int, device: int = 0, dtype: str = "f32"):
         self._h = None
@@ -267,6 +279,89 @@ class EmbeddingIndex:
         self._check_range(rc, total.value, cap, "max_pairs")
         n = total.value
         return np.stack([oi[:n], oj[:n]], axis=1), score[:n].copy()
+
+    def rows_at(self, ids) -> np.ndarray:
+        """The rows at ``ids`` as stored, widened to f32 [n, E], in the order of ``ids``; dead rows and
+        repeated ids are allowed, an id outside [0, len(self)) raises."""
+        x = self._ids(ids)
+        out = np.empty((x.size, self.E), np.float32)
+        check(lib().clipgpu_index_get_rows_at(self.handle, x.ctypes.data, x.size, out.ctypes.data))
+        return out
+
+    def _centroids(self, a, what: str) -> np.ndarray:
+        """``a`` as f32 [C, E] with 1 <= C <= MAX_CENTROIDS, checked before any native call."""
+        c = self._rows(a, what)
+        if not 1 <= c.shape[0] <= MAX_CENTROIDS:
+            raise ValueError(f"the number of centroids must be in 1..{MAX_CENTROIDS}, got {c.shape[0]}")
+        return c
+
+    def assign(self, centroids, logit_scale: float = 1.0, logit_bias: float = 0.0, allow=None
+               ) -> Tuple[np.ndarray, np.ndarray]:
+        """The nearest of ``centroids`` [C, E] for every row: (labels int64 [len(self)], scores f32
+        [len(self)]).  ``labels[j]`` is what ``search(row j, 1)`` of an index holding the centroids returns
+        (highest score, equal scores to the lower centroid, a NaN below -inf) and ``scores[j]`` has the bits
+        of ``similarity(centroids, rows(), "logits")[labels[j], j]``; a row that is dead or not allowed by
+        ``allow`` (as in ``search``) gets (-1, -inf).  1 <= C <= 65536."""
+        words = self._allow_words(allow)
+        c = self._centroids(centroids, "centroids")
+        labels = np.empty(len(self), np.int64)
+        scores = np.empty(len(self), np.float32)
+        check(lib().clipgpu_index_assign(self.handle, c.ctypes.data, c.shape[0], float(logit_scale), float(logit_bias),
+                                         None if words is None else words.ctypes.data, labels.ctypes.data,
+                                         scores.ctypes.data))
+        return labels, scores
+
+    def assign_device(self, d_centroids: int, C: int, d_label: int, d_score: int, logit_scale: float = 1.0,
+                      logit_bias: float = 0.0, stream: int = 0, d_allow: int = 0) -> None:
+        """``assign`` on device pointers (centroids f32 [C, E], 16-byte aligned, in; labels int32
+        [len(self)] and scores f32 [len(self)] out), ordered on ``stream``; returns without synchronising."""
+        check(lib().clipgpu_index_assign_device(self.handle, c_void_p(d_centroids), int(C), float(logit_scale),
+                                                float(logit_bias), c_void_p(d_allow or None), c_void_p(d_label),
+                                                c_void_p(d_score), c_void_p(stream or None)))
+
+    def kmeans(self, n_clusters=None, init=None, max_iter: int = 25, seed: int = 0, allow=None) -> "KMeansResult":
+        """Spherical k-means over the live (and allowed) rows: Lloyd iterations of ``assign`` (scale 1, bias
+        0) and an update whose sums are 64-bit integers (include/clipgpu.h has the arithmetic), so the result
+        does not depend on the order of the rows: a repeated run and a permuted gallery give the same bits.
+        ``init`` [C, E] is the start, used as given; with ``init=None`` the start is the stored rows at
+        ``np.sort(np.random.default_rng(seed).choice(live allowed ids, n_clusters, replace=False))``.  Stops
+        when no label changes or after ``max_iter`` assignments-and-updates; either way ``labels`` and
+        ``scores`` are exactly ``assign(centroids)``.  An empty cluster keeps its centroid (``counts`` says
+        which): re-seeding is the caller's business.  Returns a ``KMeansResult``."""
+        if isinstance(max_iter, bool) or not isinstance(max_iter, (int, np.integer)):
+            raise TypeError(f"max_iter must be an integer, got {type(max_iter).__name__}")
+        if int(max_iter) < 1:
+            raise ValueError(f"max_iter must be at least 1, got {int(max_iter)}")
+        words = self._allow_words(allow)
+        if init is not None:
+            cen = self._centroids(init, "init").copy()
+            if n_clusters is not None and int(n_clusters) != cen.shape[0]:
+                raise ValueError(f"n_clusters is {int(n_clusters)} but init has {cen.shape[0]} rows")
+        else:
+            if n_clusters is None:
+                raise ValueError("n_clusters is required when init is None")
+            if isinstance(n_clusters, bool) or not isinstance(n_clusters, (int, np.integer)):
+                raise TypeError(f"n_clusters must be an integer, got {type(n_clusters).__name__}")
+            if not 1 <= int(n_clusters) <= MAX_CENTROIDS:
+                raise ValueError(f"n_clusters must be in 1..{MAX_CENTROIDS}, got {int(n_clusters)}")
+            ok = self.is_live()
+            if allow is not None:
+                ok &= np.asarray(allow)
+            ids = np.flatnonzero(ok)
+            if int(n_clusters) > ids.size:
+                raise ValueError(f"n_clusters is {int(n_clusters)} but only {ids.size} rows are live and allowed")
+            cen = self.rows_at(np.sort(np.random.default_rng(seed).choice(ids, int(n_clusters), replace=False)))
+        C = cen.shape[0]
+        labels = np.empty(len(self), np.int64)
+        scores = np.empty(len(self), np.float32)
+        counts = np.empty(C, np.int64)
+        moved = np.empty(int(max_iter), np.int64)
+        iters = ctypes.c_int64(0)
+        check(lib().clipgpu_index_kmeans(self.handle, C, cen.ctypes.data, int(max_iter),
+                                         None if words is None else words.ctypes.data, labels.ctypes.data,
+                                         scores.ctypes.data, counts.ctypes.data, moved.ctypes.data,
+                                         ctypes.addressof(iters)))
+        return KMeansResult(cen, labels, scores, counts, moved[:iters.value].copy(), int(iters.value))
 
     @staticmethod
     def _prob_args(k, activation) -> Tuple[int, int]:

@@ -386,7 +386,47 @@ int clipgpu_similarity_device(const float* d_img, int64_t n_img, const float* d_
  * Limits, refused with CLIPGPU_ERR_INVALID before any device call: a NULL handle or output, nq <= 0 or an
  * empty index ("Empty batch"), nq > 2^31 - 1 (a record holds an int32 query index), a NaN threshold, and
  * capacity / max_results / max_pairs outside 1 .. 2^28 (2^28 records are 3 GiB of device memory and, for
- * the host forms, twice that in host memory while they sort). */
+ * the host forms, twice that in host memory while they sort).
+ *
+ * Assignment and k-means.  clipgpu_index_assign[_device] give, for every slot j < size, the nearest of C
+ * centroids (f32 [C][E] whatever the gallery's type; the _device form wants them 16-byte aligned):
+ *   label[j] = the centroid a clipgpu_index_search with k = 1 of an index holding the C centroids returns for
+ *     the query g_j (row j as stored): the highest score, equal scores to the lower centroid index, a NaN
+ *     below -inf; score[j] = fmaf(dot(c_label, g_j), logit_scale, logit_bias) with the bits of
+ *     clipgpu_similarity(centroids, rows, logits)[label][j] (the score is symmetric bit for bit);
+ *   a row that is dead or not allowed (`allow` / `d_allow` as in the filtered search) gets (-1, -inf), the
+ *     search's empty entry.  Nothing at or past `size` is written.
+ *   _device form: d_label int32 [size], d_score f32 [size]; ordered after the handle's last operation, does
+ *     not synchronise.  Host form: out_label int64 [size], out_score f32 [size]; the centroids, labels and
+ *     scores pass through buffers the handle allocates at the first such call, grows on demand and keeps
+ *     until it is destroyed (a failed allocation is CLIPGPU_ERR_DEVICE and leaves the index usable).
+ *   One launch covers the gallery: a block owns 64 rows and walks all centroids, so there is no span cut,
+ *     no row chunk and no merge, and clipgpu_test_topk_span_cols / clipgpu_test_topk_route change nothing.
+ * clipgpu_index_kmeans runs spherical Lloyd iterations over the live allowed rows, from the C centroids in
+ * `centroids` (host, in: the start, out: the result), with logit_scale 1 and logit_bias 0 (cosines on unit
+ * rows).  With n = the live allowed rows:
+ *   for t = 1, 2, ...: labels_t = assign(centroids_{t-1}); moved_t = the live allowed rows whose label differs
+ *     from labels_{t-1} (moved_1 = n); moved_t == 0: stop, iters = t, the centroids untouched; else
+ *     centroids_t = update(labels_t); t == max_iter: stop, iters = max_iter, after one more assign -- the
+ *     labels and scores returned are ALWAYS exactly assign(the centroids returned).
+ *   out_moved[t - 1] = moved_t, entries past iters are -1; out_count[c] = the rows whose returned label is c.
+ *   update, in integers, so that it does not depend on the order rows are met in (a repeated run, a permuted
+ *     gallery and another grid give the same bits; a converged result is an exact fixed point):
+ *       m = the largest |x| over the live allowed rows as stored; e = frexp(m)'s exponent (0 if m == 0);
+ *       b = the bit length of n; s = 62 - e - b, so that |sum| < 2^62 always;
+ *       S[c][i] = sum over label_j == c of llrint(ldexp((double)g_j[i], s)), int64, round to nearest even;
+ *       with v_i = (double)S[c][i] and n2 = sum_i v_i * v_i in f64 (i ascending, multiply and add rounded
+ *       separately): if n2 > 0, centroid[c][i] = (float)(v_i / sqrt(n2)), correctly rounded divide and root.
+ *     A cluster with no member, or whose members sum to zero, keeps its previous centroid bit for bit (its
+ *     count says which): re-seeding is the caller's business.
+ *   A non-finite element in a live allowed row is CLIPGPU_ERR_INVALID, the message names the first such row.
+ *   The call holds the handle's mutex throughout and synchronises once per iteration (it reads moved_t).
+ *   Buffers as the host assign's, plus the sums (C * E * 8 bytes).
+ * clipgpu_index_get_rows_at copies the rows at ids[0 .. n) (host; dead rows and repeats allowed; the range
+ * rules of clipgpu_index_set_rows) as stored, widened to f32, in the order of ids, to out_rows [n][E] (host):
+ * what a caller seeds k-means with.
+ * Refused with CLIPGPU_ERR_INVALID before any device call: a NULL handle, input or output; C outside
+ * 1 .. 65536; max_iter < 1; an empty index ("Empty batch"). */
 typedef struct clipgpu_index clipgpu_index;
 #define CLIPGPU_TOPK_MAX 128
 enum clipgpu_index_dtype { CLIPGPU_INDEX_F32 = 0, CLIPGPU_INDEX_F16 = 1, CLIPGPU_INDEX_BF16 = 2 };
@@ -428,6 +468,15 @@ int clipgpu_index_range_search(clipgpu_index* ix, const float* queries, int64_t 
 int clipgpu_index_self_join(clipgpu_index* ix, float threshold, float logit_scale, float logit_bias,
                             const uint32_t* allow, int64_t max_pairs, int64_t* out_i, int64_t* out_j, float* out_score,
                             int64_t* out_total);
+int clipgpu_index_get_rows_at(clipgpu_index* ix, const int64_t* ids, int64_t n, float* out_rows);
+int clipgpu_index_assign_device(clipgpu_index* ix, const float* d_centroids, int64_t C, float logit_scale,
+                                float logit_bias, const uint32_t* d_allow, int32_t* d_label, float* d_score,
+                                void* stream);
+int clipgpu_index_assign(clipgpu_index* ix, const float* centroids, int64_t C, float logit_scale, float logit_bias,
+                         const uint32_t* allow, int64_t* out_label, float* out_score);
+int clipgpu_index_kmeans(clipgpu_index* ix, int64_t C, float* centroids, int64_t max_iter, const uint32_t* allow,
+                         int64_t* out_label, float* out_score, int64_t* out_count, int64_t* out_moved,
+                         int64_t* out_iters);
 
 /* ---- data-parallel sharding + the RCCL all-gather (north_star: "batches shard
  * data-parallel across the 8 GPUs of one node with an RCCL all-gather over xGMI only for the final

@@ -286,6 +286,14 @@ int clipgpu_test_topk_narrow_rows(void);
 /* Host only: the search's order key (csrc/kernels/topk_key.hpp) of (score, gallery index): a larger
  * key ranks first. */
 int clipgpu_test_topk_key(float score, uint32_t index, uint64_t* key);
+/* The integer sums S [C][E] of the last update clipgpu_index_kmeans ran on this handle (C must be that
+ * call's), copied to out_sums (host), and the shift s they were taken with.  Refused if no update ran. */
+int clipgpu_test_index_kmeans_sums(struct clipgpu_index* ix, int64_t C, int64_t* out_sums, int* out_shift);
+/* One k-means update alone, for the benchmark: zeroes the handle's sums, adds the rows under d_label (device
+ * int32 [size], every label -1 or below C) at `shift` and finalises into d_centroids (device f32 [C][E]), on
+ * `stream`, without synchronising.  The sums stay for clipgpu_test_index_kmeans_sums. */
+int clipgpu_test_index_kmeans_update(struct clipgpu_index* ix, const int32_t* d_label, int64_t C, int shift,
+                                     float* d_centroids, void* stream);
 
 #ifdef __cplusplus
 }

@@ -355,6 +355,94 @@ def topk_range_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 16, 256), dt
         print(json.dumps(out), flush=True)
 
 
+def kmeans_leg(N=1 << 20, E=512, runs=7, warmup=2, Cs=(64, 1024), dtypes=("f32", "f16")):
+    """One k-means iteration over a device-resident gallery, per centroid count and storage type, in its two
+    halves and against what a user can do without them; legs alternating in one process (rotating order,
+    device-event timings after `warmup` rounds):
+      assign       clipgpu_index_assign_device, every row's nearest of C centroids;
+      range        the yardstick: range_search_device of the same gallery with the C centroids as queries at a
+                   threshold nothing passes -- the same FLOPs through the same tile loop;
+      update       one update alone (clipgpu_test_index_kmeans_update: zero the sums, 64-bit integer atomic adds,
+                   finalise);
+      search_k1    the assignment today: search_device with k = 1 of every gallery row (widened to f32) against
+                   an index of the centroids;
+      index_add    the sums today: torch index_add_ of the widened rows into an f32 [C][E] tensor (float atomics;
+                   without the normalisation).
+    assign's labels and scores are checked against search_k1's, bit for bit.  The line also carries the wall
+    clock of a whole EmbeddingIndex.kmeans of 3 iterations from host centroids (copies included)."""
+    from open_clip_inference import EmbeddingIndex
+    torch.manual_seed(0)
+    L = _lib.lib()
+    s = torch.cuda.current_stream().cuda_stream
+    g = torch.nn.functional.normalize(torch.randn(N, E, device="cuda"), dim=1)
+    for dt in dtypes:
+        esz, tdt = INDEX_DTYPES[dt]
+        gw = g if tdt is None else g.to(tdt).float()  # what the index holds, widened
+        with EmbeddingIndex(E, N, dtype=dt) as ix:
+            ix.add_device(g.data_ptr(), N, s)
+            for C in Cs:
+                cen = gw[torch.randperm(N, device="cuda")[:C]].contiguous()
+                new_cen = cen.clone()
+                lab, sc = torch.empty(N, dtype=torch.int32, device="cuda"), torch.empty(N, device="cuda")
+                idx1, sc1 = torch.empty((N, 1), dtype=torch.int64, device="cuda"), torch.empty((N, 1), device="cuda")
+                rec = (torch.empty(1024, dtype=torch.int32, device="cuda"), torch.empty(1024, dtype=torch.int32, device="cuda"),
+                       torch.empty(1024, device="cuda"))
+                tot = torch.zeros(1, dtype=torch.int64, device="cuda")
+                sums = torch.zeros((C, E), device="cuda")
+                shift = 62 - 1 - int(N).bit_length()  # unit rows: m <= 1
+                with EmbeddingIndex(E, C) as cix:
+                    cix.add_device(cen.data_ptr(), C, s)
+                    ix.assign_device(cen.data_ptr(), C, lab.data_ptr(), sc.data_ptr(), 1.0, 0.0, s)
+                    torch.cuda.synchronize()
+                    lab64 = lab.long()
+
+                    def update():
+                        _lib.check(L.clipgpu_test_index_kmeans_update(ix.handle, lab.data_ptr(), C, shift, new_cen.data_ptr(), s))
+
+                    def index_add():
+                        sums.zero_()
+                        sums.index_add_(0, lab64, gw)
+
+                    legs = [("assign", lambda: ix.assign_device(cen.data_ptr(), C, lab.data_ptr(), sc.data_ptr(), 1.0, 0.0, s)),
+                            ("range", lambda: ix.range_search_device(cen.data_ptr(), C, 1e30, 1024, rec[0].data_ptr(),
+                                                                     rec[1].data_ptr(), rec[2].data_ptr(), tot.data_ptr(),
+                                                                     1.0, 0.0, s)),
+                            ("update", update),
+                            ("search_k1", lambda: cix.search_device(gw.data_ptr(), N, 1, idx1.data_ptr(), sc1.data_ptr(),
+                                                                    1.0, 0.0, s)),
+                            ("index_add", index_add)]
+                    ms = {name: [] for name, _ in legs}
+                    for rnd in range(warmup + runs):
+                        r = rnd % len(legs)
+                        for name, fn in legs[r:] + legs[:r]:  # every leg follows every other equally often
+                            t = _event_ms(fn)
+                            if rnd >= warmup:
+                                ms[name].append(t)
+                    assert int(tot) == 0
+                    assert torch.equal(lab.long(), idx1[:, 0]) and torch.equal(sc.view(torch.int32), sc1[:, 0].view(torch.int32))
+                    # the update against the float sums of the baseline, loosely: the same centroids
+                    ref = torch.nn.functional.normalize(sums.double(), dim=1).float()
+                    err = float((new_cen - ref).abs().max())
+                    assert err < 1e-5, err
+                host_cen = cen.cpu().numpy()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                km = ix.kmeans(init=host_cen, max_iter=3)
+                wall = (time.perf_counter() - t0) * 1e3
+                out = {"measure": "kmeans", "C": C, "dtype": dt, "N": N, "E": E, "runs": runs, "shift": shift,
+                       "same_labels_as_search_k1": True, "update_max_abs_diff_vs_float_sums": err,
+                       "kmeans_3_iters_wall_ms": round(wall, 1), "kmeans_moved": km.moved.tolist()}
+                for name, v in ms.items():
+                    out[name] = _stats(v, N * E * esz)
+                m = {name: out[name]["ms_median"] for name in ms}
+                out["assign_over_range"] = round(m["assign"] / m["range"], 3)
+                out["assign_over_search_k1"] = round(m["assign"] / m["search_k1"], 3)
+                out["update_over_assign"] = round(m["update"] / m["assign"], 3)
+                out["update_over_index_add"] = round(m["update"] / m["index_add"], 3)
+                out["update_atomics_per_us"] = round(N * E / (m["update"] * 1e3), 0)
+                print(json.dumps(out), flush=True)
+
+
 def topk_routes_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 2, 4, 8, 12, 16)):
     """The measurement kNarrowRows (csrc/kernels/kernels.hpp) is set by: for every query count the
     few-query kernel can take, that kernel (route 2) against the wide one (route 1) on an f32 gallery,
@@ -583,6 +671,8 @@ if __name__ == "__main__":
         topk_probs_leg()
     if "topkrange" in which:  # the range search against search k = 10, dense emission, and the self-join
         topk_range_leg()
+    if "kmeans" in which:  # one k-means iteration: assign against the range search, the integer-sum update
+        kmeans_leg()
     if "so400m" in which:
         device_leg("so400m_vision", SO400M_16_SIGLIP2_384_CFG, 0, 128)
     if "h14" in which:
