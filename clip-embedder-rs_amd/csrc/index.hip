@@ -31,9 +31,18 @@
 // assigns every slot under the search's mask; there is no span cut and no chunking, a block owns 64 gallery
 // rows.  k-means alternates that launch with an integer-sum update and reads one counter back per iteration;
 // its labels, scores, centroids and sums live in buffers of the handle's, lazy like the record buffer.
+//
+// Inverted lists and the probed search (clipgpu_index_partition, clipgpu_index_search_probed[_device];
+// kernels/lists.hip, kernels/probe.hip).  partition assigns the live rows to the given centroids and sorts their
+// ids by label into CSR lists (device) whose offsets it also keeps on the host; add, add_device, set_rows and
+// clear mark the partition stale, remove does not (the live bit rejects the row at search time).  A probed
+// search is, per chunk of queries: a coarse launch_topk over the handle's centroid copy, the probe kernel over
+// (query, probed list, part of the list) into the search workspace, and the search's merge.  The parts per list
+// and the rows per chunk come from the host's offsets and the workspace's size, so nothing synchronises.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <mutex>
@@ -54,6 +63,10 @@ namespace {
 constexpr int64_t kQueryChunk = 256;  // queries per launch: 4 query tiles
 constexpr int kMaxBlocks = 1024;      // phase-1 blocks per launch the workspace is sized for (4 per CU)
 inline size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
+
+// Test hooks of the probed search (clipgpu_test_probe_parts, clipgpu_test_probe_chunk); 0 = the default.
+std::atomic<int> g_probe_parts{0};
+std::atomic<int> g_probe_chunk{0};
 
 }  // namespace
 
@@ -90,6 +103,19 @@ struct clipgpu_index {
   int64_t cl_sum_n = 0;
   int64_t km_C = 0;              // the last update's centroid count (0 = none yet) and shift, for
   int km_shift = 0;              // clipgpu_test_index_kmeans_sums
+  // the partition (clipgpu_index_partition); lazy, grown on demand, freed with the handle:
+  char* pt_ids = nullptr;        // the lists' row ids int32 [pt_ids_n]
+  int64_t pt_ids_n = 0;
+  char* pt_off = nullptr;        // their offsets int32 [pt_off_n + 1]
+  int64_t pt_off_n = 0;
+  char* pt_cen = nullptr;        // the partition's own copy of the centroids f32 [pt_cen_n][E]
+  int64_t pt_cen_n = 0;
+  char* pt_coarse = nullptr;     // the coarse step of a probed search: indices int64 and scores f32
+                                 // [kQueryChunk][kTopkMax], and the host form's staged probes (int64, as many)
+  int64_t pt_C = 0;              // the lists of the partition in force; 0 = none
+  bool pt_stale = false;         // rows were added, replaced or cleared since
+  std::vector<int32_t> pt_h_off; // the offsets on the host [pt_C + 1]
+  int64_t pt_longest = 0;        // the longest list
   hipStream_t stream = nullptr;  // the host-buffer forms' stream
   hipEvent_t done = nullptr;     // recorded after every device-side operation
 };
@@ -428,9 +454,197 @@ void fetch_assignment(clipgpu_index* ix, const int32_t* d_label, const float* d_
   for (size_t i = 0; i < l.size(); ++i) out_label[i] = l[i];
 }
 
+
+// ---- the partition and the probed search (kernels/lists.hip, kernels/probe.hip) ---------------------------
+// The regions of pt_coarse.
+constexpr size_t kCoarseEntries = (size_t)kQueryChunk * kTopkMax;
+int64_t* coarse_idx(clipgpu_index* ix) { return (int64_t*)ix->pt_coarse; }
+float* coarse_score(clipgpu_index* ix) { return (float*)(ix->pt_coarse + kCoarseEntries * 8); }
+int64_t* coarse_probes(clipgpu_index* ix) { return (int64_t*)(ix->pt_coarse + kCoarseEntries * 12); }
+
+void drop_partition(clipgpu_index* ix) {
+  ix->pt_C = 0;
+  ix->pt_stale = false;
+  ix->pt_h_off = std::vector<int32_t>();
+  ix->pt_longest = 0;
+}
+
+// One probed search call.  q, allow and the outputs: device pointers for probed_on and probed_device, host
+// pointers for probed_host.  probes: [nq][nprobe] or NULL.
+struct ProbedReq { const float* q; int64_t nq, k, nprobe; float scale, bias; const uint32_t* allow; };
+struct ProbedOut { int64_t* idx; float* score; int64_t* probes; };
+
+// The refusals that need no lock, then the lock and the partition's state: all before any device call.
+std::unique_lock<std::mutex> enter_probed(clipgpu_index* ix, const ProbedReq& r, const ProbedOut& o) {
+  if (!ix || !r.q || !o.idx || !o.score) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+  if (r.nq <= 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
+  if (r.k < 1 || r.k > CLIPGPU_TOPK_MAX)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "k must be in 1.." + std::to_string(CLIPGPU_TOPK_MAX) +
+                                           " (clipgpu_similarity gives the whole matrix)");
+  if (r.nprobe < 1 || r.nprobe > CLIPGPU_TOPK_MAX)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "nprobe must be in 1.." + std::to_string(CLIPGPU_TOPK_MAX) + ", got " +
+                                           std::to_string(r.nprobe));
+  std::unique_lock<std::mutex> lk(ix->mu);
+  if (ix->pt_C == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "the index has no partition (clipgpu_index_partition)");
+  if (ix->pt_stale)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "the partition is stale: rows were added, replaced or cleared since "
+                                       "clipgpu_index_partition (call it again)");
+  HIP_CHECK(hipSetDevice(ix->device));
+  return lk;
+}
+
+// Searches the device rows r.q on `s` under one mask into the device buffers of `o`, in chunks sized so that
+// the workspace holds every block's k entries.  Per chunk: the coarse search of the centroid copy (launch_topk
+// into pt_coarse; it has finished with the workspace before the probe kernel starts, by stream order), the
+// probe kernel, the merge.  Nothing here synchronises.
+void probed_on(clipgpu_index* ix, const ProbedReq& r, const uint32_t* mask, const ProbedOut& o, hipStream_t s) {
+  const int C = (int)ix->pt_C, k = (int)r.k, E = (int)ix->E;
+  const int np = (int)std::min<int64_t>(r.nprobe, C);  // the lists a query reads
+  const long ws_entries = (long)ix->ws_blocks * 64 * kTopkMax;
+  // the parts of a list: enough blocks to fill the GPU, no more parts than the longest list has tiles
+  const long tiles = std::max<long>(1, (ix->pt_longest + 15) / 16);
+  const long rows0 = std::min<int64_t>(kQueryChunk, r.nq);
+  long S = std::min(tiles, std::max(1L, (kNarrowSpans + rows0 * np - 1) / (rows0 * np)));
+  if (g_probe_parts.load() > 0) S = g_probe_parts.load();
+  S = std::max(1L, std::min(S, std::min(65535L / np, ws_entries / ((long)np * k))));
+  long chunk = std::min<long>(kQueryChunk, ws_entries / ((long)np * S * k));
+  if (g_probe_chunk.load() > 0) chunk = std::min<long>(chunk, g_probe_chunk.load());
+  if (o.probes && np < r.nprobe) HIP_CHECK(hipMemsetAsync(o.probes, 0xff, (size_t)r.nq * r.nprobe * 8, s));  // -1
+  for (int64_t q0 = 0; q0 < r.nq; q0 += chunk) {
+    const int rows = (int)std::min<int64_t>(chunk, r.nq - q0);
+    const float* q = r.q + q0 * E;
+    const TopkPlan p = topk_plan(C, rows, ix->ws_blocks);
+    HIP_CHECK(launch_topk({q, rows, ix->pt_cen, TOPK_GAL_F32, C, E, 1.f, 0.f, np, p, ix->d_ws, nullptr, coarse_idx(ix),
+                           coarse_score(ix), TOPK_PROBS_NONE, nullptr, 0, nullptr, nullptr, s}));
+    if (o.probes)
+      HIP_CHECK(hipMemcpy2DAsync(o.probes + q0 * r.nprobe, (size_t)r.nprobe * 8, coarse_idx(ix), (size_t)np * 8,
+                                 (size_t)np * 8, rows, hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(launch_probe({q, rows, ix->gallery, ix->dtype, (int)ix->size, E, r.scale, r.bias, k, coarse_idx(ix), np,
+                            (int)S, (const int32_t*)ix->pt_off, (const int32_t*)ix->pt_ids, mask, ix->d_ws, s}));
+    HIP_CHECK(launch_topk_merge(ix->d_ws, rows, np * (int)S, k, o.idx + q0 * k, o.score + q0 * k, s));
+  }
+  mark_last(ix, s);
+}
+
+int probed_device(clipgpu_index* ix, const ProbedReq& r, const ProbedOut& o, hipStream_t s) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_probed(ix, r, o);
+    order_after_last(ix, s);
+    probed_on(ix, r, build_mask(ix, r.allow, s), o, s);
+  });
+}
+
+int probed_host(clipgpu_index* ix, const ProbedReq& r, const ProbedOut& o) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_probed(ix, r, o);
+    HIP_CHECK(hipEventSynchronize(ix->done));  // the staging buffers and the filter area are free
+    if (r.allow) HIP_CHECK(copy_h2d(ix->d_eff, r.allow, (size_t)live_words(ix->size) * 4));
+    const uint32_t* mask = build_mask(ix, r.allow ? ix->d_eff : nullptr, ix->stream);
+    const ProbedOut st = {ix->st_idx, ix->st_score, o.probes ? coarse_probes(ix) : nullptr};
+    for (int64_t q0 = 0; q0 < r.nq; q0 += kQueryChunk) {
+      const ProbedReq c = {ix->st_q, std::min(kQueryChunk, r.nq - q0), r.k, r.nprobe, r.scale, r.bias, nullptr};
+      HIP_CHECK(copy_h2d(ix->st_q, r.q + q0 * ix->E, (size_t)c.nq * ix->E * 4));
+      probed_on(ix, c, mask, st, ix->stream);
+      HIP_CHECK(hipStreamSynchronize(ix->stream));
+      HIP_CHECK(copy_d2h(o.idx + q0 * r.k, st.idx, (size_t)c.nq * r.k * 8));
+      HIP_CHECK(copy_d2h(o.score + q0 * r.k, st.score, (size_t)c.nq * r.k * 4));
+      if (st.probes) HIP_CHECK(copy_d2h(o.probes + q0 * r.nprobe, st.probes, (size_t)c.nq * r.nprobe * 8));
+    }
+  });
+}
+
 }  // namespace
 
 extern "C" {
+
+int clipgpu_index_partition(clipgpu_index* ix, const float* centroids, int64_t C, int64_t* out_counts) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_cluster(ix, !centroids, C);
+    HIP_CHECK(hipEventSynchronize(ix->done));  // the filter area, the cluster buffers and the scratch are free
+    drop_partition(ix);                        // a failure below leaves the index without a partition, usable
+    const ClusterBuf b = cluster_buffers(ix, C, false);
+    grow(ix->pt_ids, ix->pt_ids_n, ix->size, (size_t)ix->size * 4);
+    grow(ix->pt_off, ix->pt_off_n, C, (size_t)(C + 1) * 4);
+    grow(ix->pt_cen, ix->pt_cen_n, C, (size_t)C * ix->E * 4);
+    if (!ix->pt_coarse) HIP_CHECK(hipMalloc((void**)&ix->pt_coarse, kCoarseEntries * 20));
+    void* tmp = scratch_bytes(ix, lists_tmp_bytes(ix->size));
+    hipStream_t s = ix->stream;
+    HIP_CHECK(copy_h2d(ix->pt_cen, centroids, (size_t)C * ix->E * 4));
+    // the labels of clipgpu_index_assign(centroids, 1, 0, NULL): -1 marks a dead row, which is in no list
+    assign_on(ix, (const float*)ix->pt_cen, C, 1.f, 0.f, build_mask(ix, nullptr, s), b.label[0], b.score, s);
+    HIP_CHECK(launch_lists(b.label[0], (int)ix->size, (int)C, (int32_t*)ix->pt_off, (int32_t*)ix->pt_ids, tmp, s));
+    mark_last(ix, s);
+    HIP_CHECK(hipStreamSynchronize(s));
+    std::vector<int32_t> off((size_t)C + 1);
+    HIP_CHECK(copy_d2h(off.data(), ix->pt_off, off.size() * 4));
+    int64_t longest = 0;
+    for (int64_t c = 0; c < C; ++c) {
+      const int64_t n = (int64_t)off[c + 1] - off[c];
+      longest = std::max(longest, n);
+      if (out_counts) out_counts[c] = n;
+    }
+    ix->pt_h_off.swap(off);
+    ix->pt_longest = longest;
+    ix->pt_C = C;
+  });
+}
+
+int64_t clipgpu_index_partition_lists(const clipgpu_index* ix) {
+  if (!ix) return 0;
+  std::lock_guard<std::mutex> lk(const_cast<clipgpu_index*>(ix)->mu);
+  return ix->pt_C == 0 ? 0 : ix->pt_stale ? -1 : ix->pt_C;
+}
+
+int clipgpu_index_get_lists(clipgpu_index* ix, int64_t* out_offsets, int64_t* out_ids) {
+  return guarded([&]() {
+    if (!ix || !out_offsets || !out_ids) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (ix->pt_C == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "the index has no partition (clipgpu_index_partition)");
+    if (ix->pt_stale) throw ClipErr(CLIPGPU_ERR_INVALID, "the partition is stale (call clipgpu_index_partition again)");
+    for (size_t c = 0; c < ix->pt_h_off.size(); ++c) out_offsets[c] = ix->pt_h_off[c];
+    std::vector<int32_t> ids((size_t)ix->pt_h_off.back());
+    if (ids.empty()) return;
+    HIP_CHECK(hipSetDevice(ix->device));
+    HIP_CHECK(hipEventSynchronize(ix->done));
+    HIP_CHECK(copy_d2h(ids.data(), ix->pt_ids, ids.size() * 4));
+    for (size_t i = 0; i < ids.size(); ++i) out_ids[i] = ids[i];
+  });
+}
+
+int clipgpu_index_drop_partition(clipgpu_index* ix) {
+  return guarded([&]() {
+    if (!ix) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    drop_partition(ix);  // the buffers stay for the next partition; destroy frees them
+  });
+}
+
+int clipgpu_index_search_probed(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, int64_t nprobe,
+                                float logit_scale, float logit_bias, const uint32_t* allow, int64_t* out_idx,
+                                float* out_score, int64_t* out_probes) {
+  return probed_host(ix, {queries, nq, k, nprobe, logit_scale, logit_bias, allow}, {out_idx, out_score, out_probes});
+}
+
+int clipgpu_index_search_probed_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k, int64_t nprobe,
+                                       float logit_scale, float logit_bias, const uint32_t* d_allow, int64_t* d_idx,
+                                       float* d_score, int64_t* d_probes, void* stream) {
+  return probed_device(ix, {d_queries, nq, k, nprobe, logit_scale, logit_bias, d_allow}, {d_idx, d_score, d_probes},
+                       (hipStream_t)stream);
+}
+
+int clipgpu_test_probe_parts(int parts) {
+  return guarded([&]() {
+    if (parts < 0) throw ClipErr(CLIPGPU_ERR_INVALID, "parts must be >= 0 (0 = default)");
+    g_probe_parts.store(parts);
+  });
+}
+
+int clipgpu_test_probe_chunk(int rows) {
+  return guarded([&]() {
+    if (rows < 0) throw ClipErr(CLIPGPU_ERR_INVALID, "rows must be >= 0 (0 = default)");
+    g_probe_chunk.store(rows);
+  });
+}
 
 int clipgpu_index_range_search_device(clipgpu_index* ix, const float* d_queries, int64_t nq, float threshold,
                                       float logit_scale, float logit_bias, const uint32_t* d_allow, int64_t capacity,
@@ -567,6 +781,10 @@ void clipgpu_index_destroy(clipgpu_index* ix) {
   if (ix->cl_rows) (void)hipFree(ix->cl_rows);
   if (ix->cl_cen) (void)hipFree(ix->cl_cen);
   if (ix->cl_sum) (void)hipFree(ix->cl_sum);
+  if (ix->pt_ids) (void)hipFree(ix->pt_ids);
+  if (ix->pt_off) (void)hipFree(ix->pt_off);
+  if (ix->pt_cen) (void)hipFree(ix->pt_cen);
+  if (ix->pt_coarse) (void)hipFree(ix->pt_coarse);
   if (ix->work) (void)hipFree(ix->work);
   if (ix->gallery) (void)hipFree(ix->gallery);
   delete ix;
@@ -583,6 +801,7 @@ int clipgpu_index_clear(clipgpu_index* ix) {
     if (!ix) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
     std::lock_guard<std::mutex> lk(ix->mu);
     ix->size = 0;  // a later add overwrites the rows only after the last search (the `done` event)
+    ix->pt_stale = true;
     ix->h_live = std::vector<uint32_t>();  // every future row is live
     ix->n_dead = 0;
   });
@@ -641,6 +860,7 @@ int clipgpu_index_set_rows(clipgpu_index* ix, const int64_t* ids, const float* r
       HIP_CHECK(hipStreamSynchronize(ix->stream));
     });
     if (!ix->h_live.empty() && mark_rows(ix, ids, n, true)) upload_live(ix);  // the rows are live again
+    ix->pt_stale = true;
     mark_last(ix, ix->stream);
   });
 }
@@ -659,6 +879,7 @@ int clipgpu_index_add_device(clipgpu_index* ix, const float* d_rows, int64_t n, 
       HIP_CHECK(launch_gal_round(ix->dtype, d_rows, dst, n * ix->E, s));
     mark_last(ix, s);
     ix->size += n;
+    ix->pt_stale = true;
   });
 }
 
@@ -679,6 +900,7 @@ int clipgpu_index_add(clipgpu_index* ix, const float* rows, int64_t n) {
       });
     }
     ix->size += n;
+    ix->pt_stale = true;
   });
 }
 

@@ -247,6 +247,45 @@ hipError_t launch_topk(const TopkArgs& a);
 long topk_mask_words(long n);
 hipError_t launch_topk_mask(const uint32_t* live, const uint32_t* allow, uint32_t* eff, long n, hipStream_t s);
 
+// Phase 2 alone, without probabilities: per query row the k best of its n_spans * k workspace entries (ws, the
+// layout phase 1 writes: [nq][n_spans][k] entries of 8 bytes) to out_idx / out_score [nq][k].  For a phase 1 of
+// another translation unit (kernels/probe.hip).  n_spans <= 65535, n_spans * k <= INT32_MAX.
+hipError_t launch_topk_merge(const void* ws, int nq, int n_spans, int k, int64_t* out_idx, float* out_score,
+                             hipStream_t s);
+
+// Inverted lists (kernels/lists.hip): the CSR of the rows by label.  label: int32 [N], -1 = not in any list,
+// else below C (1 <= C <= kClusterMaxCentroids).  offsets int32 [C + 1]: offsets[c] = the rows with a label
+// below c; ids int32 [offsets[C]]: the rows of list c at [offsets[c], offsets[c + 1]), ascending -- a pure
+// function of the labels: a stable counting sort by 8-bit digits (one pass for C <= 256, else two), no atomic
+// decides a position.  tmp: lists_tmp_bytes(N) bytes of scratch, 256-byte aligned.  Nothing is read back: the
+// launches are asynchronous on the stream.
+size_t lists_tmp_bytes(long N);
+hipError_t launch_lists(const int32_t* label, int N, int C, int32_t* offsets, int32_t* ids, void* tmp, hipStream_t s);
+
+// Probed phase 1 (kernels/probe.hip): launch_topk's few-query phase 1 over the rows of chosen lists.  Block
+// (query q, probe p, part s), one wave: list = coarse[q * n_probe + p]; of the list's ceil(len / 16) 16-row
+// tiles it takes [s * T, (s + 1) * T), T = ceil(tiles / parts); the gallery row of list position pos is
+// ids[pos], its key topk_key(score bits, ids[pos]), its allowed bit mask[id >> 5] >> (id & 31) (mask NULL:
+// every row).  Its k best go to ws[((q * n_probe + p) * parts + s) * k ..], k empty entries if its tile range
+// or its list is empty: the layout launch_topk_merge reads with n_spans = n_probe * parts.  The score is
+// launch_topk's, bit for bit.  nq <= 65535, n_probe * parts <= 65535; every id must lie below N.
+struct ProbeArgs {
+  const float* q;  // [nq][E]
+  int nq;
+  const void* g;  // [N][E] of dtype (TopkGal)
+  int dtype, N, E;
+  float scale, bias;
+  int k;
+  const int64_t* coarse;  // [nq][n_probe]: list numbers, each below the number of lists (or negative: no list)
+  int n_probe, parts;
+  const int32_t* offsets;  // [lists + 1]
+  const int32_t* ids;
+  const uint32_t* mask;
+  void* ws;
+  hipStream_t stream;
+};
+hipError_t launch_probe(const ProbeArgs& a);
+
 // Range search (kernels/range.hip): every (query row, gallery row) whose score -- launch_topk's score,
 // bit for bit -- is >= threshold as an f32 comparison (a NaN score never passes), appended to a bounded
 // record buffer in no particular order.  One launch: nq query rows (the wide kernel, or the few-query one

@@ -46,6 +46,7 @@
 #include "gallery.hpp"
 #include "kernels.hpp"
 #include "topk_key.hpp"
+#include "topk_select.hpp"
 #include "topk_stage.hpp"
 
 namespace clipgpu {
@@ -55,46 +56,12 @@ std::atomic<int> g_topk_route{0};
 
 namespace {
 
-// (TB, TK, KQ, LDT, NB, the staging layout and the gallery element as loaded: topk_stage.hpp)
-constexpr int CAND1 = 32;  // phase 1 candidate slots per row (one ballot adds at most 16 to a row)
+// (TB, TK, KQ, LDT, NB, the staging layout and the gallery element as loaded: topk_stage.hpp;
+// CAND1, ent_key, ent_empty and compact_row: topk_select.hpp)
 constexpr int CAND2 = 64;  // phase 2 (one ballot adds at most 64)
 #ifndef CLIPGPU_TOPK_MERGE_STEPS
 #define CLIPGPU_TOPK_MERGE_STEPS 4  // 64-entry steps the merge loads at once
 #endif
-
-// A selection entry: x = the score's own f32 bits, y = gallery index.  Compared by topk_key.
-__device__ __forceinline__ uint64_t ent_key(uint2 e) { return topk_key(e.x, e.y); }
-__device__ __forceinline__ uint2 ent_empty() { return make_uint2(kTopkEmptyScore, kTopkEmptyIndex); }
-
-// Wave-cooperative (all 64 lanes, uniform arguments).  ent[0 .. k) is the row's current best list,
-// ent[k .. k + c) its candidates (k + c <= 192).  Leaves the k best of both in ent[0 .. k), best
-// first, and returns the key of ent[k - 1]: the row's new threshold (0 while the list has empty
-// slots).  Empty entries all have key 0; the position breaks that tie, so ranks are a permutation.
-__device__ __forceinline__ uint64_t compact_row(uint2* ent, int k, int c, int lane) {
-  const int m = k + c;
-  uint2 mine[3];
-  uint64_t mk[3];
-  int rank[3];
-#pragma unroll
-  for (int s = 0; s < 3; ++s) {
-    const int i = lane + 64 * s;
-    mine[s] = i < m ? ent[i] : ent_empty();
-    mk[s] = ent_key(mine[s]);
-    rank[s] = 0;
-  }
-  for (int j = 0; j < m; ++j) {
-    const uint64_t kj = ent_key(ent[j]);  // same address in every lane: an LDS broadcast
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-      if (64 * s < m) rank[s] += (kj > mk[s] || (kj == mk[s] && j < lane + 64 * s)) ? 1 : 0;
-  }
-  wave_lds_order();
-#pragma unroll
-  for (int s = 0; s < 3; ++s)
-    if (lane + 64 * s < m && rank[s] < k) ent[rank[s]] = mine[s];
-  wave_lds_order();
-  return ent_key(ent[k - 1]);
-}
 
 // ---- softmax normaliser (PROBS instantiations) -----------------------------------------------------
 // A row's running pair (m, s): m = the largest logit fed so far, s = sum exp(l - m) over them, by online
@@ -678,6 +645,16 @@ TopkPlan topk_plan(long N, int nq, int max_blocks) {
   p.span_cols = (int)((tiles + want - 1) / want) * TB;
   p.n_spans = (int)((N + p.span_cols - 1) / p.span_cols);
   return p;
+}
+
+hipError_t launch_topk_merge(const void* ws, int nq, int n_spans, int k, int64_t* out_idx, float* out_score,
+                             hipStream_t s) {
+  if (!ws || !out_idx || !out_score || nq <= 0 || n_spans <= 0 || n_spans > 65535 || k < 1 || k > kTopkMax ||
+      (long)n_spans * k > INT32_MAX)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(topk_merge_kernel<TOPK_PROBS_NONE>, dim3((nq + 3) / 4), dim3(256), 0, s, (const uint2*)ws, nq,
+                     n_spans, k, out_idx, out_score, (const float2*)nullptr, (float*)nullptr, (float*)nullptr);
+  return hipGetLastError();
 }
 
 hipError_t launch_topk(const TopkArgs& a) {

@@ -91,6 +91,14 @@ _PROTOS = [
     ("clipgpu_index_assign", c_int, [c_void_p, c_void_p, c_int64, c_float, c_float, c_void_p, c_void_p, c_void_p]),
     ("clipgpu_index_kmeans", c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p]),
+    ("clipgpu_index_partition", c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    ("clipgpu_index_partition_lists", c_int64, [c_void_p]),
+    ("clipgpu_index_get_lists", c_int, [c_void_p, c_void_p, c_void_p]),
+    ("clipgpu_index_drop_partition", c_int, [c_void_p]),
+    ("clipgpu_index_search_probed", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_float, c_void_p,
+                                            c_void_p, c_void_p, c_void_p]),
+    ("clipgpu_index_search_probed_device", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_float,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("clipgpu_comm_unique_id", c_int, [c_void_p]),
     ("clipgpu_comm_init_rank", c_int, [c_void_p, c_void_p, c_int, c_int]),
     ("clipgpu_comm_info", c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
@@ -114,6 +122,8 @@ _PROTOS = [
     ("clipgpu_test_topk_route", c_int, [c_int]),
     ("clipgpu_test_topk_narrow_rows", c_int, []),
     ("clipgpu_test_topk_key", c_int, [c_float, ctypes.c_uint32, POINTER(c_uint64)]),
+    ("clipgpu_test_probe_parts", c_int, [c_int]),
+    ("clipgpu_test_probe_chunk", c_int, [c_int]),
     ("clipgpu_test_index_kmeans_sums", c_int, [c_void_p, c_int64, c_void_p, POINTER(c_int)]),
     ("clipgpu_test_index_kmeans_update", c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     ("clipgpu_test_gemm_lnf", c_int, [c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,

@@ -133,15 +133,21 @@ class Clip:
         index.add(embs)
         return index
 
-    def search(self, index, texts: Sequence[str], k: int, allow=None) -> List[List[Tuple[int, float]]]:
+    def search(self, index, texts: Sequence[str], k: int, allow=None, nprobe=None
+               ) -> List[List[Tuple[int, float]]]:
         """Semantic search (examples/search.rs; rank_images, src/clip.rs:134-170, cut to its k best):
         per text the k best rows of ``index`` as (gallery index, logit), best first, equal logits by
         ascending index.  The logits use the model's logit_scale / logit_bias (defaults 1.0 / 0.0).
         Logits, not probabilities: ``rank`` returns the probabilities.  Removed rows never appear; ``allow`` (a bool array
         [len(index)]) restricts the search to the rows where it is True, and a text gets fewer than k
-        pairs when fewer rows are allowed."""
+        pairs when fewer rows are allowed.  ``nprobe`` (None: every row, as always) searches only the
+        ``nprobe`` lists of the index's partition closest to each text (``EmbeddingIndex.search_probed``)."""
         scale, bias = self._scale_bias()
-        idx, score = index.search(self.text.embed_texts(texts), k, float(scale), float(bias), allow=allow)
+        if nprobe is None:
+            idx, score = index.search(self.text.embed_texts(texts), k, float(scale), float(bias), allow=allow)
+        else:
+            idx, score = index.search_probed(self.text.embed_texts(texts), k, nprobe, float(scale), float(bias),
+                                             allow=allow)
         return [[(int(i), float(s)) for i, s in zip(ri, rs) if i >= 0] for ri, rs in zip(idx, score)]
 
     def search_above(self, index, texts: Sequence[str], min_logit: float, allow=None, max_results: int = 1 << 20

@@ -56,7 +56,9 @@ class EmbeddingIndex:
     with the softmax (over all searched rows) or sigmoid probabilities of the k results.  ``range_search``
     returns every row at or above a score threshold instead of the k best, and ``duplicates`` joins the
     gallery against itself at a threshold; neither builds the score matrix.  ``assign`` gives every row its
-    nearest of C centroids and ``kmeans`` puts the rows into groups, reproducibly."""
+    nearest of C centroids and ``kmeans`` puts the rows into groups, reproducibly.  ``partition`` cuts the
+    gallery into inverted lists by nearest centroid and ``search_probed`` searches only the ``nprobe`` lists
+    closest to each query: approximate in which rows it looks at, exact in what it returns for them."""
 
     def __init__(self, E: int, capacity: int, device: int = 0, dtype: str = "f32"):
         self._h = None
@@ -408,3 +410,80 @@ class EmbeddingIndex:
                                                       float(logit_bias), act, c_void_p(d_allow or None),
                                                       c_void_p(d_idx), c_void_p(d_score), c_void_p(d_prob),
                                                       c_void_p(d_norm or None), c_void_p(stream or None)))
+
+    # ---- inverted lists and the probed search ----------------------------------------------------------
+    def partition(self, centroids) -> np.ndarray:
+        """Cuts the gallery into ``C`` inverted lists: list c holds the live rows whose ``assign(centroids)``
+        label is c, ids ascending; a row dead now is in no list.  ``centroids`` [C, E] (1 <= C <= 65536) are
+        copied into the index.  Returns the list lengths, int64 [C].  ``remove`` keeps the partition valid;
+        ``add``, ``add_device``, ``set_rows`` and ``clear`` make it stale (``n_lists == -1``) until
+        ``partition`` is called again, which costs an ``assign`` plus a few milliseconds."""
+        c = self._centroids(centroids, "centroids")
+        counts = np.empty(c.shape[0], np.int64)
+        check(lib().clipgpu_index_partition(self.handle, c.ctypes.data, c.shape[0], counts.ctypes.data))
+        return counts
+
+    def partition_kmeans(self, n_lists: int, max_iter: int = 25, seed: int = 0) -> "KMeansResult":
+        """``kmeans(n_lists, max_iter=max_iter, seed=seed)`` followed by ``partition`` of its centroids;
+        returns the ``KMeansResult`` (its ``counts`` are the list lengths)."""
+        km = self.kmeans(n_lists, max_iter=max_iter, seed=seed)
+        self.partition(km.centroids)
+        return km
+
+    @property
+    def n_lists(self) -> int:
+        """The number of lists of the partition, 0 if there is none, -1 if it is stale."""
+        return int(lib().clipgpu_index_partition_lists(self.handle))
+
+    def lists(self) -> Tuple[np.ndarray, np.ndarray]:
+        """The partition as CSR: (offsets int64 [C + 1], ids int64 [offsets[C]]); list c is
+        ``ids[offsets[c]:offsets[c + 1]]``, ascending."""
+        offsets = np.zeros(max(self.n_lists, 0) + 1, np.int64)
+        ids = np.empty(len(self), np.int64)
+        check(lib().clipgpu_index_get_lists(self.handle, offsets.ctypes.data, ids.ctypes.data))
+        return offsets, ids[:offsets[-1]].copy()
+
+    def drop_partition(self) -> None:
+        check(lib().clipgpu_index_drop_partition(self.handle))
+
+    @staticmethod
+    def _probe_args(k, nprobe) -> Tuple[int, int]:
+        """(k, nprobe), checked before any native call."""
+        for name, v in (("k", k), ("nprobe", nprobe)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"{name} must be an integer, got {type(v).__name__}")
+            if not 1 <= int(v) <= TOPK_MAX:
+                raise ValueError(f"{name} must be in 1..{TOPK_MAX}, got {int(v)}")
+        return int(k), int(nprobe)
+
+    def search_probed(self, queries, k: int, nprobe: int, logit_scale: float = 1.0, logit_bias: float = 0.0,
+                      allow=None, return_probes: bool = False):
+        """``search`` over the ``nprobe`` lists whose centroids are closest to each query (by the dot product,
+        equal ones to the lower list): per query exactly -- ids, order and score bits -- what
+        ``search(query, k, ..., allow=mask)`` returns with ``mask`` = the rows of those lists that are live and
+        allowed.  A row outside the probed lists is never found: that is the whole approximation.
+        ``nprobe >= n_lists`` is ``search`` itself.  1 <= nprobe <= 128.  ``return_probes=True`` adds the probed
+        lists, int64 [nq, nprobe], best first, -1 past ``n_lists``.  Raises if there is no partition or it is
+        stale."""
+        k, nprobe = self._probe_args(k, nprobe)
+        words = self._allow_words(allow)
+        q = self._rows(queries, "queries")
+        idx = np.empty((q.shape[0], k), np.int64)
+        score = np.empty((q.shape[0], k), np.float32)
+        probes = np.empty((q.shape[0], nprobe), np.int64) if return_probes else None
+        check(lib().clipgpu_index_search_probed(self.handle, q.ctypes.data, q.shape[0], k, nprobe, float(logit_scale),
+                                                float(logit_bias), None if words is None else words.ctypes.data,
+                                                idx.ctypes.data, score.ctypes.data,
+                                                None if probes is None else probes.ctypes.data))
+        return (idx, score, probes) if return_probes else (idx, score)
+
+    def search_probed_device(self, d_queries: int, nq: int, k: int, nprobe: int, d_idx: int, d_score: int,
+                             logit_scale: float = 1.0, logit_bias: float = 0.0, stream: int = 0, d_allow: int = 0,
+                             d_probes: int = 0) -> None:
+        """``search_probed`` on device pointers (as ``search_device``; ``d_probes`` int64 [nq, nprobe] out or 0 =
+        not wanted), ordered on ``stream``; returns without synchronising."""
+        k, nprobe = self._probe_args(k, nprobe)
+        check(lib().clipgpu_index_search_probed_device(self.handle, c_void_p(d_queries), int(nq), k, nprobe,
+                                                       float(logit_scale), float(logit_bias),
+                                                       c_void_p(d_allow or None), c_void_p(d_idx), c_void_p(d_score),
+                                                       c_void_p(d_probes or None), c_void_p(stream or None)))

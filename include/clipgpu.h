@@ -426,7 +426,40 @@ int clipgpu_similarity_device(const float* d_img, int64_t n_img, const float* d_
  * rules of clipgpu_index_set_rows) as stored, widened to f32, in the order of ids, to out_rows [n][E] (host):
  * what a caller seeds k-means with.
  * Refused with CLIPGPU_ERR_INVALID before any device call: a NULL handle, input or output; C outside
- * 1 .. 65536; max_iter < 1; an empty index ("Empty batch"). */
+ * 1 .. 65536; max_iter < 1; an empty index ("Empty batch").
+ *
+ * Inverted lists and the probed search (IVF).  clipgpu_index_partition fixes, at the moment it is called,
+ *   label[j] = the label clipgpu_index_assign(centroids, 1.0, 0.0, NULL) returns for row j, for every live row
+ *     j < size (exactly one label >= 0 each; a row with NaN scores still has a largest key), and
+ *   list c   = the live rows with label c, ids ascending; a row dead at that moment is in no list.
+ * centroids: host f32 [C][E], copied into the handle; 1 <= C <= 65536; out_counts (NULL = not wanted) receives
+ * the C list lengths.  The lists are a pure function of the labels (a stable counting sort on the device: the
+ * same bits on every run).  The call synchronises.  clipgpu_index_partition_lists returns C, 0 if there is no
+ * partition, -1 if it is stale; clipgpu_index_get_lists copies the CSR to the host: out_offsets int64 [C + 1],
+ * out_ids int64 [out_offsets[C]] (the caller sizes it with size, or from the counts); clipgpu_index_drop_partition
+ * forgets the partition.
+ *   clipgpu_index_search_probed[_device] return, for each query q, bit for bit what
+ * clipgpu_index_search_filtered(q, k, logit_scale, logit_bias, allow = A_q) returns, where A_q is the set of
+ * rows that are live now, allowed by `allow` (as in the filtered search) and whose label is in P_q, and P_q is
+ * the index set a clipgpu_index_search with k = min(nprobe, C), scale 1, bias 0 of an F32 index holding the C
+ * centroids returns for q (the largest keys; equal scores to the lower centroid).  The result carries the
+ * original row ids and the scores' own bits, (-1, -inf) past min(k, |A_q|), and equal scores come out by
+ * ascending row id whatever list or position the rows sit in.  It is approximate only in which rows it looks at.
+ * 1 <= nprobe <= CLIPGPU_TOPK_MAX; nprobe >= C is the filtered search, exactly.  out_probes / d_probes (NULL =
+ * not wanted): int64 [nq][nprobe], P_q best first, -1 past min(nprobe, C).  A query reads its nprobe lists and
+ * the C centroids instead of the gallery: per chunk of queries one coarse search of the handle's centroid copy,
+ * one launch over (query, probed list, part of the list) and the search's merge, in the workspace allocated at
+ * creation.  The _device form is ordered after the handle's last operation and does not synchronise.
+ *   clipgpu_index_remove keeps the partition valid: the id stays in its list and is rejected by the live bit
+ * at search time.  clipgpu_index_add, _add_device, _set_rows and _clear make it STALE: a probed search (and
+ * clipgpu_index_get_lists) is then CLIPGPU_ERR_INVALID, before any device call, with a message that says
+ * "stale"; with no partition at all the message says "no partition".  clipgpu_index_partition may be called
+ * again at any time and replaces the old partition (an assignment plus the list build; there is no
+ * incremental insertion).  The partition's buffers (ids and offsets, 4 bytes per row and list; the centroid
+ * copy; 640 KiB for the coarse results) are allocated at the first partition, grown on demand and kept until
+ * the handle is destroyed; the list build passes through the handle's scratch buffer (about 5 bytes per row).
+ * Refused with CLIPGPU_ERR_INVALID before any device call: a NULL handle, input or output; C outside
+ * 1 .. 65536; nq <= 0 or an empty index ("Empty batch"); k or nprobe outside 1 .. CLIPGPU_TOPK_MAX. */
 typedef struct clipgpu_index clipgpu_index;
 #define CLIPGPU_TOPK_MAX 128
 enum clipgpu_index_dtype { CLIPGPU_INDEX_F32 = 0, CLIPGPU_INDEX_F16 = 1, CLIPGPU_INDEX_BF16 = 2 };
@@ -477,6 +510,16 @@ int clipgpu_index_assign(clipgpu_index* ix, const float* centroids, int64_t C, f
 int clipgpu_index_kmeans(clipgpu_index* ix, int64_t C, float* centroids, int64_t max_iter, const uint32_t* allow,
                          int64_t* out_label, float* out_score, int64_t* out_count, int64_t* out_moved,
                          int64_t* out_iters);
+int clipgpu_index_partition(clipgpu_index* ix, const float* centroids, int64_t C, int64_t* out_counts);
+int64_t clipgpu_index_partition_lists(const clipgpu_index* ix); /* C; 0 = no partition; -1 = stale */
+int clipgpu_index_get_lists(clipgpu_index* ix, int64_t* out_offsets, int64_t* out_ids);
+int clipgpu_index_drop_partition(clipgpu_index* ix);
+int clipgpu_index_search_probed(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, int64_t nprobe,
+                                float logit_scale, float logit_bias, const uint32_t* allow, int64_t* out_idx,
+                                float* out_score, int64_t* out_probes);
+int clipgpu_index_search_probed_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k,
+                                       int64_t nprobe, float logit_scale, float logit_bias, const uint32_t* d_allow,
+                                       int64_t* d_idx, float* d_score, int64_t* d_probes, void* stream);
 
 /* ---- data-parallel sharding + the RCCL all-gather (north_star: "batches shard
  * data-parallel across the 8 GPUs of one node with an RCCL all-gather over xGMI only for the final

@@ -295,6 +295,15 @@ int clipgpu_test_index_kmeans_sums(struct clipgpu_index* ix, int64_t C, int64_t*
 int clipgpu_test_index_kmeans_update(struct clipgpu_index* ix, const int32_t* d_label, int64_t C, int shift,
                                      float* d_centroids, void* stream);
 
+/* The parts a probed list is cut into (clipgpu_index_search_probed: blocks per (query, probed list); 0 = the
+ * default, chosen from the longest list so that the launch fills the GPU), process-wide and atomic, for every
+ * probed search started afterwards.  A value above a list's number of 16-row tiles leaves blocks with nothing to
+ * do, which write empty entries.  Capped by what the workspace holds.  The result never depends on it. */
+int clipgpu_test_probe_parts(int parts);
+/* The most query rows of one probed launch (0 = the default, as many as the workspace holds, at most 256), as
+ * above: small inputs then run several chunks.  The result never depends on it. */
+int clipgpu_test_probe_chunk(int rows);
+
 #ifdef __cplusplus
 }
 #endif

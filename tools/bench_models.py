@@ -443,6 +443,96 @@ def kmeans_leg(N=1 << 20, E=512, runs=7, warmup=2, Cs=(64, 1024), dtypes=("f32",
                 print(json.dumps(out), flush=True)
 
 
+def ivf_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Cs=(256, 1024, 4096), nprobes=(1, 8, 32), Qs=(1, 16, 256),
+            dtypes=("f32", "f16"), centres=1024, sigma=0.05):
+    """The probed (IVF) search against the plain search, per storage type, list count, query count and nprobe.
+    The gallery is CLUSTERED: unit rows around `centres` random centres (centre + sigma * Gaussian noise per
+    element); the queries are fresh draws of the same mixture.  The Gaussian gallery of the other legs has
+    nothing to partition.  Per (dtype, C): partition_kmeans (5 iterations) and then, per Q, legs alternating in one
+    process (rotating order, device-event timings after `warmup` rounds): search_device -- unchanged code, the
+    yardstick measured in the same process -- and search_probed_device at each nprobe.  Beside each probed leg:
+    the rows read as a fraction of the gallery (the probed lists' lengths, mean over the queries) and recall@k
+    against the plain search (a property of the data, reported, not a bar).  One-off costs: the wall clock of
+    partition (assign + list build, synchronous) and of assign_device alone (device events); their difference
+    is the build.  The one timing condition: at Q = 1, C = 1024, nprobe = 8, f32 the probed [min, max] lies
+    wholly below the plain [min, max]; asserted after the lines are printed."""
+    from open_clip_inference import EmbeddingIndex
+    torch.manual_seed(0)
+    s = torch.cuda.current_stream().cuda_stream
+    cen0 = torch.nn.functional.normalize(torch.randn(centres, E, device="cuda"), dim=1)
+
+    def draw(n):
+        return torch.nn.functional.normalize(cen0[torch.randint(0, centres, (n,), device="cuda")] +
+                                             sigma * torch.randn(n, E, device="cuda"), dim=1).contiguous()
+
+    g = draw(N)
+    qs = {Q: draw(Q) for Q in Qs}
+    verdict = None
+    for dt in dtypes:
+        esz, _ = INDEX_DTYPES[dt]
+        with EmbeddingIndex(E, N, dtype=dt) as ix:
+            ix.add_device(g.data_ptr(), N, s)
+            torch.cuda.synchronize()
+            for C in Cs:
+                t0 = time.perf_counter()
+                km = ix.partition_kmeans(C, max_iter=5, seed=0)
+                km_wall = (time.perf_counter() - t0) * 1e3
+                t0 = time.perf_counter()
+                counts = ix.partition(km.centroids)
+                part_wall = (time.perf_counter() - t0) * 1e3
+                dc = torch.from_numpy(km.centroids).cuda()
+                lab, sc = torch.empty(N, dtype=torch.int32, device="cuda"), torch.empty(N, device="cuda")
+                assign_ms = [_event_ms(lambda: ix.assign_device(dc.data_ptr(), C, lab.data_ptr(), sc.data_ptr(), 1.0, 0.0, s))
+                             for _ in range(3)]
+                lens = torch.from_numpy(counts).cuda()
+                print(json.dumps({"measure": "ivf_partition", "dtype": dt, "N": N, "E": E, "C": C,
+                                  "partition_kmeans_5_iters_wall_ms": round(km_wall, 1),
+                                  "partition_wall_ms": round(part_wall, 2), "assign_device_ms": round(min(assign_ms), 2),
+                                  "build_ms_by_difference": round(part_wall - min(assign_ms), 2),
+                                  "longest_list": int(counts.max()), "empty_lists": int((counts == 0).sum())}), flush=True)
+                for Q in Qs:
+                    q = qs[Q]
+                    names = ["plain"] + [f"nprobe{p}" for p in nprobes]
+                    res = {n: (torch.empty((Q, k), dtype=torch.int64, device="cuda"), torch.empty((Q, k), device="cuda"))
+                           for n in names}
+                    prb = {p: torch.empty((Q, p), dtype=torch.int64, device="cuda") for p in nprobes}
+
+                    def plain():
+                        ix.search_device(q.data_ptr(), Q, k, res["plain"][0].data_ptr(), res["plain"][1].data_ptr(), 100.0, 0.0, s)
+
+                    def probed(p):
+                        n = f"nprobe{p}"
+                        return lambda: ix.search_probed_device(q.data_ptr(), Q, k, p, res[n][0].data_ptr(), res[n][1].data_ptr(),
+                                                               100.0, 0.0, s, 0, prb[p].data_ptr())
+
+                    legs = [("plain", plain)] + [(f"nprobe{p}", probed(p)) for p in nprobes]
+                    ms = {n: [] for n in names}
+                    for rnd in range(warmup + runs):
+                        r = rnd % len(legs)
+                        for name, fn in legs[r:] + legs[:r]:  # every leg follows every other equally often
+                            t = _event_ms(fn)
+                            if rnd >= warmup:
+                                ms[name].append(t)
+                    want = res["plain"][0].cpu().numpy()
+                    out = {"measure": "ivf_search", "dtype": dt, "N": N, "E": E, "C": C, "Q": Q, "k": k, "runs": runs,
+                           "plain": _stats(ms["plain"], N * E * esz)}
+                    for p in nprobes:
+                        n = f"nprobe{p}"
+                        got = res[n][0].cpu().numpy()
+                        recall = float(np.mean([len(set(a) & set(b)) for a, b in zip(got.tolist(), want.tolist())])) / k
+                        frac = float(lens[prb[p].clamp(min=0)].sum(dim=1).double().mean()) / N
+                        st = _stats(ms[n], N * E * esz)
+                        del st["gallery_TBps"]
+                        st.update({"rows_read_fraction": round(frac, 5), f"recall_at_{k}": round(recall, 4),
+                                   "plain_over_probed": round(out["plain"]["ms_median"] / st["ms_median"], 2)})
+                        out[n] = st
+                    print(json.dumps(out), flush=True)
+                    if dt == "f32" and C == 1024 and Q == 1 and 8 in nprobes:
+                        verdict = (max(ms["nprobe8"]), min(ms["plain"]))
+    if verdict is not None:
+        assert verdict[0] < verdict[1], f"probed max {verdict[0]} ms is not below plain min {verdict[1]} ms"
+
+
 def topk_routes_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 2, 4, 8, 12, 16)):
     """The measurement kNarrowRows (csrc/kernels/kernels.hpp) is set by: for every query count the
     few-query kernel can take, that kernel (route 2) against the wide one (route 1) on an f32 gallery,
@@ -673,6 +763,8 @@ if __name__ == "__main__":
         topk_range_leg()
     if "kmeans" in which:  # one k-means iteration: assign against the range search, the integer-sum update
         kmeans_leg()
+    if "ivf" in which:  # the probed search against the plain search on a clustered gallery
+        ivf_leg()
     if "so400m" in which:
         device_leg("so400m_vision", SO400M_16_SIGLIP2_384_CFG, 0, 128)
     if "h14" in which:
