@@ -39,6 +39,13 @@
 // search is, per chunk of queries: a coarse launch_topk over the handle's centroid copy, the probe kernel over
 // (query, probed list, part of the list) into the search workspace, and the search's merge.  The parts per list
 // and the rows per chunk come from the host's offsets and the workspace's size, so nothing synchronises.
+//
+// Int8 codes and the coded search (clipgpu_index_enable_codes, clipgpu_index_search_coded[_device];
+// kernels/codes.hip).  Once enabled, the codes are a second device array beside the gallery: add, add_device and
+// set_rows code the rows they write, on the same stream, after the gallery write.  A coded search is, per chunk
+// of queries: the queries' codes, the coarse scan of the gallery's codes and the search's merge with k = refine
+// (the candidates), then the probe kernel over each query's candidates as a list of its own and the merge again.
+// An index whose codes were never enabled runs none of this.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -67,6 +74,9 @@ inline size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
 // Test hooks of the probed search (clipgpu_test_probe_parts, clipgpu_test_probe_chunk); 0 = the default.
 std::atomic<int> g_probe_parts{0};
 std::atomic<int> g_probe_chunk{0};
+// Test hook of the coded search (clipgpu_test_codes_stage): 0 = both stages, 1 = the coarse stage only, 2 = the
+// re-rank only, on the candidates the last coarse stage left.
+std::atomic<int> g_codes_stage{0};
 
 }  // namespace
 
@@ -116,6 +126,11 @@ struct clipgpu_index {
   bool pt_stale = false;         // rows were added, replaced or cleared since
   std::vector<int32_t> pt_h_off; // the offsets on the host [pt_C + 1]
   int64_t pt_longest = 0;        // the longest list
+  // the int8 codes (clipgpu_index_enable_codes); allocated there, freed by drop_codes or with the handle:
+  int8_t* cd_codes = nullptr;    // [capacity][cd_Ep], cd_Ep = E rounded up to 64; NULL = no codes
+  float* cd_scale = nullptr;     // [capacity]
+  char* cd_work = nullptr;       // a coded search in flight: the regions carve_codes places
+  int64_t cd_Ep = 0;
   hipStream_t stream = nullptr;  // the host-buffer forms' stream
   hipEvent_t done = nullptr;     // recorded after every device-side operation
 };
@@ -553,6 +568,132 @@ int probed_host(clipgpu_index* ix, const ProbedReq& r, const ProbedOut& o) {
   });
 }
 
+// ---- int8 codes and the coded search (kernels/codes.hip) --------------------------------------------------
+// The regions of cd_work: the staged codes and scales of a chunk of queries, the chunk's merged candidates and
+// their coarse scores, and the candidates as the lists the probe kernel reads.
+struct CodesWork { int8_t* qc; float* qs; int64_t* cand; float* coarse; int32_t* ids; int32_t* off; int64_t* lists; };
+size_t carve_codes(const clipgpu_index* ix, CodesWork* w) {
+  size_t off = 0, chunk = (size_t)kQueryChunk;
+  char* base = ix->cd_work;
+  CodesWork c;
+  c.qc = carve<int8_t>(base, off, chunk * ix->cd_Ep);
+  c.qs = carve<float>(base, off, chunk * 4);
+  c.cand = carve<int64_t>(base, off, chunk * kTopkMax * 8);
+  c.coarse = carve<float>(base, off, chunk * kTopkMax * 4);
+  c.ids = carve<int32_t>(base, off, chunk * kTopkMax * 4);
+  c.off = carve<int32_t>(base, off, (2 * chunk + 1) * 4);
+  c.lists = carve<int64_t>(base, off, chunk * 8);
+  if (w) *w = c;
+  return off;
+}
+
+void free_codes(clipgpu_index* ix) {
+  if (ix->cd_codes) (void)hipFree(ix->cd_codes);
+  if (ix->cd_scale) (void)hipFree(ix->cd_scale);
+  if (ix->cd_work) (void)hipFree(ix->cd_work);
+  ix->cd_codes = nullptr;
+  ix->cd_scale = nullptr;
+  ix->cd_work = nullptr;
+}
+
+// Codes rows ids[0 .. n) (device ids) or [first, first + n) of the gallery on `s`, behind the write of those
+// rows on the same stream.  Nothing if the index has no codes.
+void code_rows(clipgpu_index* ix, const int64_t* d_ids, int64_t first, int64_t n, hipStream_t s) {
+  if (!ix->cd_codes || n <= 0) return;
+  HIP_CHECK(launch_codes_quant({ix->gallery, ix->dtype, (long)n, (int)ix->E, (int)ix->cd_Ep, d_ids, (long)first,
+                                ix->cd_codes, ix->cd_scale, s}));
+}
+
+// One coded search call.  q, allow and the outputs: device pointers for coded_on and coded_device, host pointers
+// for coded_host.  cand, coarse: [nq][refine] or NULL.
+struct CodedReq { const float* q; int64_t nq, k, refine; float scale, bias; const uint32_t* allow; };
+struct CodedOut { int64_t* idx; float* score; int64_t* cand; float* coarse; };
+
+// The refusals that need no lock, then the lock and the codes: all before any device call.
+std::unique_lock<std::mutex> enter_coded(clipgpu_index* ix, const CodedReq& r, const CodedOut& o) {
+  if (!ix || !r.q || !o.idx || !o.score) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+  if (r.nq <= 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
+  if (r.k < 1 || r.k > CLIPGPU_TOPK_MAX)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "k must be in 1.." + std::to_string(CLIPGPU_TOPK_MAX) +
+                                           " (clipgpu_similarity gives the whole matrix)");
+  if (r.refine < r.k || r.refine > CLIPGPU_TOPK_MAX)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "refine must be in k.." + std::to_string(CLIPGPU_TOPK_MAX) + ", got " +
+                                           std::to_string(r.refine));
+  std::unique_lock<std::mutex> lk(ix->mu);
+  if (!ix->cd_codes) throw ClipErr(CLIPGPU_ERR_INVALID, "the index has no codes (clipgpu_index_enable_codes)");
+  if (ix->size == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");  // an empty gallery
+  HIP_CHECK(hipSetDevice(ix->device));
+  return lk;
+}
+
+// Searches the device rows r.q on `s` under one mask into the device buffers of `o`, in chunks of kQueryChunk
+// rows.  Per chunk, the coarse stage: the queries' codes, the scan (the search's route and span cut) and the merge
+// with k = refine into cd_work; then the re-rank: the candidates as lists, the probe kernel over list 2q for
+// query q (the candidates passed the mask already), the merge.  Stream order keeps the two users of the
+// workspace apart.  Nothing here synchronises.
+void coded_on(clipgpu_index* ix, const CodedReq& r, const uint32_t* mask, const CodedOut& o, hipStream_t s) {
+  const int E = (int)ix->E, k = (int)r.k, R = (int)r.refine, stage = g_codes_stage.load();
+  const long ws_entries = (long)ix->ws_blocks * 64 * kTopkMax;
+  CodesWork w;
+  carve_codes(ix, &w);
+  for (int64_t q0 = 0; q0 < r.nq; q0 += kQueryChunk) {
+    const int rows = (int)std::min(kQueryChunk, r.nq - q0);
+    const float* q = r.q + q0 * E;
+    if (stage != 2) {
+      HIP_CHECK(launch_codes_quant({q, TOPK_GAL_F32, rows, E, (int)ix->cd_Ep, nullptr, 0, w.qc, w.qs, s}));
+      const TopkPlan p = topk_plan(ix->size, rows, ix->ws_blocks);
+      HIP_CHECK(launch_codes_scan({w.qc, rows, ix->cd_codes, ix->cd_scale, (int)ix->size, (int)ix->cd_Ep, r.scale < 0.f,
+                                   R, p, ix->d_ws, mask, s}));
+      HIP_CHECK(launch_topk_merge(ix->d_ws, rows, p.n_spans, R, w.cand, w.coarse, s));
+      if (o.cand)
+        HIP_CHECK(hipMemcpyAsync(o.cand + q0 * R, w.cand, (size_t)rows * R * 8, hipMemcpyDeviceToDevice, s));
+      if (o.coarse)
+        HIP_CHECK(hipMemcpyAsync(o.coarse + q0 * R, w.coarse, (size_t)rows * R * 4, hipMemcpyDeviceToDevice, s));
+    }
+    if (stage != 1) {
+      HIP_CHECK(launch_codes_lists(w.cand, rows, R, w.ids, w.off, w.lists, s));
+      // the parts of a candidate list, as probed_on chooses them: enough blocks to fill the GPU, no more than tiles
+      long S = std::min<long>((R + 15) / 16, std::max(1L, (kNarrowSpans + rows - 1L) / rows));
+      if (g_probe_parts.load() > 0) S = g_probe_parts.load();
+      S = std::max(1L, std::min(S, std::min(65535L, ws_entries / ((long)rows * k))));
+      HIP_CHECK(launch_probe({q, rows, ix->gallery, ix->dtype, (int)ix->size, E, r.scale, r.bias, k, w.lists, 1, (int)S,
+                              w.off, w.ids, nullptr, ix->d_ws, s}));
+      HIP_CHECK(launch_topk_merge(ix->d_ws, rows, (int)S, k, o.idx + q0 * k, o.score + q0 * k, s));
+    }
+  }
+  mark_last(ix, s);
+}
+
+int coded_device(clipgpu_index* ix, const CodedReq& r, const CodedOut& o, hipStream_t s) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_coded(ix, r, o);
+    order_after_last(ix, s);
+    coded_on(ix, r, build_mask(ix, r.allow, s), o, s);
+  });
+}
+
+int coded_host(clipgpu_index* ix, const CodedReq& r, const CodedOut& o) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_coded(ix, r, o);
+    HIP_CHECK(hipEventSynchronize(ix->done));  // the staging buffers and the filter area are free
+    if (r.allow) HIP_CHECK(copy_h2d(ix->d_eff, r.allow, (size_t)live_words(ix->size) * 4));
+    const uint32_t* mask = build_mask(ix, r.allow ? ix->d_eff : nullptr, ix->stream);
+    CodesWork w;
+    carve_codes(ix, &w);
+    const CodedOut st = {ix->st_idx, ix->st_score, nullptr, nullptr};  // the candidates are read where the merge leaves them
+    for (int64_t q0 = 0; q0 < r.nq; q0 += kQueryChunk) {
+      const CodedReq c = {ix->st_q, std::min(kQueryChunk, r.nq - q0), r.k, r.refine, r.scale, r.bias, nullptr};
+      HIP_CHECK(copy_h2d(ix->st_q, r.q + q0 * ix->E, (size_t)c.nq * ix->E * 4));
+      coded_on(ix, c, mask, st, ix->stream);
+      HIP_CHECK(hipStreamSynchronize(ix->stream));
+      HIP_CHECK(copy_d2h(o.idx + q0 * r.k, st.idx, (size_t)c.nq * r.k * 8));
+      HIP_CHECK(copy_d2h(o.score + q0 * r.k, st.score, (size_t)c.nq * r.k * 4));
+      if (o.cand) HIP_CHECK(copy_d2h(o.cand + q0 * r.refine, w.cand, (size_t)c.nq * r.refine * 8));
+      if (o.coarse) HIP_CHECK(copy_d2h(o.coarse + q0 * r.refine, w.coarse, (size_t)c.nq * r.refine * 4));
+    }
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -643,6 +784,87 @@ int clipgpu_test_probe_chunk(int rows) {
   return guarded([&]() {
     if (rows < 0) throw ClipErr(CLIPGPU_ERR_INVALID, "rows must be >= 0 (0 = default)");
     g_probe_chunk.store(rows);
+  });
+}
+
+int clipgpu_index_enable_codes(clipgpu_index* ix) {
+  return guarded([&]() {
+    if (!ix) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (ix->E > kCodesMaxE)
+      throw ClipErr(CLIPGPU_ERR_INVALID, "codes need an embedding dim of at most " + std::to_string(kCodesMaxE) +
+                                             " (the int32 dot product of two code rows must be exact as an f32), got " +
+                                             std::to_string(ix->E));
+    if (ix->cd_codes) return;  // enabled already: the codes are current
+    HIP_CHECK(hipSetDevice(ix->device));
+    HIP_CHECK(hipEventSynchronize(ix->done));
+    ix->cd_Ep = (ix->E + 63) / 64 * 64;
+    hipError_t err = hipMalloc((void**)&ix->cd_codes, (size_t)ix->capacity * ix->cd_Ep);
+    if (err == hipSuccess) err = hipMalloc((void**)&ix->cd_scale, (size_t)ix->capacity * 4);
+    if (err == hipSuccess) err = hipMalloc((void**)&ix->cd_work, carve_codes(ix, nullptr));
+    if (err != hipSuccess) {  // the index stays usable, without codes
+      free_codes(ix);
+      HIP_CHECK(err);
+    }
+    code_rows(ix, nullptr, 0, ix->size, ix->stream);
+    mark_last(ix, ix->stream);
+  });
+}
+
+int clipgpu_index_has_codes(const clipgpu_index* ix) {
+  if (!ix) return 0;
+  std::lock_guard<std::mutex> lk(const_cast<clipgpu_index*>(ix)->mu);
+  return ix->cd_codes ? 1 : 0;
+}
+
+int clipgpu_index_drop_codes(clipgpu_index* ix) {
+  return guarded([&]() {
+    if (!ix) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (!ix->cd_codes) return;
+    HIP_CHECK(hipSetDevice(ix->device));
+    HIP_CHECK(hipEventSynchronize(ix->done));  // no search is reading them
+    free_codes(ix);
+  });
+}
+
+int clipgpu_index_get_codes(clipgpu_index* ix, int64_t first, int64_t n, int8_t* out_codes, float* out_scales) {
+  return guarded([&]() {
+    if (!ix || !out_codes || !out_scales) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (!ix->cd_codes) throw ClipErr(CLIPGPU_ERR_INVALID, "the index has no codes (clipgpu_index_enable_codes)");
+    check_row_range(ix, first, n);
+    HIP_CHECK(hipSetDevice(ix->device));
+    HIP_CHECK(hipEventSynchronize(ix->done));
+    HIP_CHECK(copy_d2h(out_scales, ix->cd_scale + first, (size_t)n * 4));
+    // rows of cd_Ep bytes on the device, of E bytes for the caller: in pieces of at most 64 MiB
+    const int64_t piece = std::min(n, std::max<int64_t>(1, (64LL << 20) / ix->cd_Ep));
+    std::vector<int8_t> h((size_t)piece * ix->cd_Ep);
+    for (int64_t r0 = 0; r0 < n; r0 += piece) {
+      const int64_t m = std::min(piece, n - r0);
+      HIP_CHECK(copy_d2h(h.data(), ix->cd_codes + (first + r0) * ix->cd_Ep, (size_t)m * ix->cd_Ep));
+      for (int64_t i = 0; i < m; ++i) memcpy(out_codes + (r0 + i) * ix->E, h.data() + i * ix->cd_Ep, (size_t)ix->E);
+    }
+  });
+}
+
+int clipgpu_index_search_coded(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, int64_t refine,
+                               float logit_scale, float logit_bias, const uint32_t* allow, int64_t* out_idx,
+                               float* out_score, int64_t* out_cand, float* out_coarse) {
+  return coded_host(ix, {queries, nq, k, refine, logit_scale, logit_bias, allow}, {out_idx, out_score, out_cand, out_coarse});
+}
+
+int clipgpu_index_search_coded_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k, int64_t refine,
+                                      float logit_scale, float logit_bias, const uint32_t* d_allow, int64_t* d_idx,
+                                      float* d_score, int64_t* d_cand, float* d_coarse, void* stream) {
+  return coded_device(ix, {d_queries, nq, k, refine, logit_scale, logit_bias, d_allow}, {d_idx, d_score, d_cand, d_coarse},
+                      (hipStream_t)stream);
+}
+
+int clipgpu_test_codes_stage(int stage) {
+  return guarded([&]() {
+    if (stage < 0 || stage > 2) throw ClipErr(CLIPGPU_ERR_INVALID, "stage must be 0 (both), 1 (coarse) or 2 (re-rank)");
+    g_codes_stage.store(stage);
   });
 }
 
@@ -785,6 +1007,9 @@ void clipgpu_index_destroy(clipgpu_index* ix) {
   if (ix->pt_off) (void)hipFree(ix->pt_off);
   if (ix->pt_cen) (void)hipFree(ix->pt_cen);
   if (ix->pt_coarse) (void)hipFree(ix->pt_coarse);
+  if (ix->cd_codes) (void)hipFree(ix->cd_codes);
+  if (ix->cd_scale) (void)hipFree(ix->cd_scale);
+  if (ix->cd_work) (void)hipFree(ix->cd_work);
   if (ix->work) (void)hipFree(ix->work);
   if (ix->gallery) (void)hipFree(ix->gallery);
   delete ix;
@@ -857,6 +1082,7 @@ int clipgpu_index_set_rows(clipgpu_index* ix, const int64_t* ids, const float* r
       HIP_CHECK(copy_h2d(f32, rows + r0 * ix->E, (size_t)m * ix->E * 4));
       HIP_CHECK(copy_h2d(d_ids, ids + r0, (size_t)m * 8));
       HIP_CHECK(launch_gal_scatter(ix->dtype, f32, (const int64_t*)d_ids, ix->gallery, m, (int)ix->E, ix->stream));
+      code_rows(ix, (const int64_t*)d_ids, 0, m, ix->stream);  // the codes of the rows just written, if enabled
       HIP_CHECK(hipStreamSynchronize(ix->stream));
     });
     if (!ix->h_live.empty() && mark_rows(ix, ids, n, true)) upload_live(ix);  // the rows are live again
@@ -877,6 +1103,7 @@ int clipgpu_index_add_device(clipgpu_index* ix, const float* d_rows, int64_t n, 
       HIP_CHECK(hipMemcpyAsync(dst, d_rows, (size_t)n * ix->E * 4, hipMemcpyDeviceToDevice, s));
     else
       HIP_CHECK(launch_gal_round(ix->dtype, d_rows, dst, n * ix->E, s));
+    code_rows(ix, nullptr, ix->size, n, s);  // the codes of the new rows, if enabled
     mark_last(ix, s);
     ix->size += n;
     ix->pt_stale = true;
@@ -898,6 +1125,10 @@ int clipgpu_index_add(clipgpu_index* ix, const float* rows, int64_t n) {
         HIP_CHECK(launch_gal_round(ix->dtype, f32, dst + r0 * ix->E * ix->esz, m * ix->E, ix->stream));
         HIP_CHECK(hipStreamSynchronize(ix->stream));
       });
+    }
+    if (ix->cd_codes) {  // the codes of the new rows, behind the synchronous copies above
+      code_rows(ix, nullptr, ix->size, n, ix->stream);
+      mark_last(ix, ix->stream);
     }
     ix->size += n;
     ix->pt_stale = true;

@@ -286,6 +286,47 @@ struct ProbeArgs {
 };
 hipError_t launch_probe(const ProbeArgs& a);
 
+// Int8 codes and the coarse scan over them (kernels/codes.hip, which has the definitions).
+constexpr int kCodesMaxE = 1024;  // |sum of E products of codes| < 2^24: exact in int32 and as an f32
+// Rows -> codes.  Row j = ids[i] (ids: device, inside src) or first + i, for i < n: src row j (E elements of
+// dtype (TopkGal), 16-byte aligned rows) becomes codes[j] (Ep bytes, Ep = E rounded up to 64, zero past E) and
+// scale[j].
+struct CodesQuantArgs {
+  const void* src;
+  int dtype;
+  long n;
+  int E, Ep;
+  const int64_t* ids;
+  long first;
+  int8_t* codes;
+  float* scale;
+  hipStream_t stream;
+};
+hipError_t launch_codes_quant(const CodesQuantArgs& a);
+// Phase 1 of the coarse stage: per (query row, span) the k largest topk_key(bits(coarse), row) over the rows
+// mask allows (as in TopkArgs), coarse = f32(dot of the codes) * gscale[row], negated if neg, to ws in the layout
+// launch_topk_merge reads.  qc [nq][Ep], gc [N][Ep], 16-byte aligned; plan: topk_plan(N, nq, ...), its
+// few-query route being the one-wave shape.
+struct CodesScanArgs {
+  const int8_t* qc;
+  int nq;
+  const int8_t* gc;
+  const float* gscale;
+  int N, Ep;
+  bool neg;
+  int k;
+  TopkPlan plan;
+  void* ws;
+  const uint32_t* mask;
+  hipStream_t stream;
+};
+hipError_t launch_codes_scan(const CodesScanArgs& a);
+// The merged candidates cand int64 [nq][refine] (-1 padded) as what launch_probe reads with n_probe = 1:
+// ids int32 [nq][refine], offsets int32 [2 nq + 1] with offsets[2q] = q * refine and offsets[2q + 1] =
+// q * refine + (valid candidates of q), lists int64 [nq] = 2q.
+hipError_t launch_codes_lists(const int64_t* cand, int nq, int refine, int32_t* ids, int32_t* offsets, int64_t* lists,
+                              hipStream_t s);
+
 // Range search (kernels/range.hip): every (query row, gallery row) whose score -- launch_topk's score,
 // bit for bit -- is >= threshold as an f32 comparison (a NaN score never passes), appended to a bounded
 // record buffer in no particular order.  One launch: nq query rows (the wide kernel, or the few-query one

@@ -99,6 +99,14 @@ _PROTOS = [
                                             c_void_p, c_void_p, c_void_p]),
     ("clipgpu_index_search_probed_device", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_float,
                                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("clipgpu_index_enable_codes", c_int, [c_void_p]),
+    ("clipgpu_index_has_codes", c_int, [c_void_p]),
+    ("clipgpu_index_drop_codes", c_int, [c_void_p]),
+    ("clipgpu_index_get_codes", c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    ("clipgpu_index_search_coded", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_float, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("clipgpu_index_search_coded_device", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_float,
+                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("clipgpu_comm_unique_id", c_int, [c_void_p]),
     ("clipgpu_comm_init_rank", c_int, [c_void_p, c_void_p, c_int, c_int]),
     ("clipgpu_comm_info", c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
@@ -124,6 +132,7 @@ _PROTOS = [
     ("clipgpu_test_topk_key", c_int, [c_float, ctypes.c_uint32, POINTER(c_uint64)]),
     ("clipgpu_test_probe_parts", c_int, [c_int]),
     ("clipgpu_test_probe_chunk", c_int, [c_int]),
+    ("clipgpu_test_codes_stage", c_int, [c_int]),
     ("clipgpu_test_index_kmeans_sums", c_int, [c_void_p, c_int64, c_void_p, POINTER(c_int)]),
     ("clipgpu_test_index_kmeans_update", c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     ("clipgpu_test_gemm_lnf", c_int, [c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,

@@ -133,7 +133,7 @@ class Clip:
         index.add(embs)
         return index
 
-    def search(self, index, texts: Sequence[str], k: int, allow=None, nprobe=None
+    def search(self, index, texts: Sequence[str], k: int, allow=None, nprobe=None, refine=None
                ) -> List[List[Tuple[int, float]]]:
         """Semantic search (examples/search.rs; rank_images, src/clip.rs:134-170, cut to its k best):
         per text the k best rows of ``index`` as (gallery index, logit), best first, equal logits by
@@ -141,9 +141,17 @@ class Clip:
         Logits, not probabilities: ``rank`` returns the probabilities.  Removed rows never appear; ``allow`` (a bool array
         [len(index)]) restricts the search to the rows where it is True, and a text gets fewer than k
         pairs when fewer rows are allowed.  ``nprobe`` (None: every row, as always) searches only the
-        ``nprobe`` lists of the index's partition closest to each text (``EmbeddingIndex.search_probed``)."""
+        ``nprobe`` lists of the index's partition closest to each text (``EmbeddingIndex.search_probed``).
+        ``refine`` (None: the exact search, as always) re-ranks the ``refine`` candidates that a scan of the index's
+        int8 codes picks per text (``EmbeddingIndex.search_coded``; the index needs ``enable_codes()``).  Giving
+        both ``refine`` and ``nprobe`` raises ``ValueError``."""
+        if refine is not None and nprobe is not None:
+            raise ValueError("give refine (the coded search) or nprobe (the probed search), not both")
         scale, bias = self._scale_bias()
-        if nprobe is None:
+        if refine is not None:
+            idx, score = index.search_coded(self.text.embed_texts(texts), k, refine, float(scale), float(bias),
+                                            allow=allow)
+        elif nprobe is None:
             idx, score = index.search(self.text.embed_texts(texts), k, float(scale), float(bias), allow=allow)
         else:
             idx, score = index.search_probed(self.text.embed_texts(texts), k, nprobe, float(scale), float(bias),

@@ -15,6 +15,7 @@ from ._lib import check, lib
 TOPK_MAX = 128  # CLIPGPU_TOPK_MAX
 RANGE_MAX = 1 << 28  # most records of a range search or a self-join (include/clipgpu.h)
 MAX_CENTROIDS = 1 << 16  # most centroids of assign and kmeans (include/clipgpu.h)
+CODES_MAX_E = 1024  # the widest rows enable_codes takes (include/clipgpu.h)
 DTYPES = {"f32": 0, "f16": 1, "bf16": 2}  # enum clipgpu_index_dtype
 PROB_ACTIVATIONS = {"softmax": 0, "sigmoid": 1}  # CLIPGPU_SIM_SOFTMAX, CLIPGPU_SIM_SIGMOID
 
@@ -58,7 +59,9 @@ class EmbeddingIndex:
     gallery against itself at a threshold; neither builds the score matrix.  ``assign`` gives every row its
     nearest of C centroids and ``kmeans`` puts the rows into groups, reproducibly.  ``partition`` cuts the
     gallery into inverted lists by nearest centroid and ``search_probed`` searches only the ``nprobe`` lists
-    closest to each query: approximate in which rows it looks at, exact in what it returns for them."""
+    closest to each query: approximate in which rows it looks at, exact in what it returns for them.
+    ``enable_codes`` adds an int8 copy of the gallery and ``search_coded`` scans that copy for ``refine``
+    candidates per query, which it re-ranks exactly: approximate in the candidates alone."""
 
     def __init__(self, E: int, capacity: int, device: int = 0, dtype: str = "f32"):
         self._h = None
@@ -487,3 +490,82 @@ class EmbeddingIndex:
                                                        float(logit_scale), float(logit_bias),
                                                        c_void_p(d_allow or None), c_void_p(d_idx), c_void_p(d_score),
                                                        c_void_p(d_probes or None), c_void_p(stream or None)))
+
+    # ---- int8 codes and the coded search ---------------------------------------------------------------
+    def enable_codes(self) -> None:
+        """Gives the index int8 codes: a second device array beside the gallery, ``capacity * (Ep + 4)`` bytes
+        (Ep = E rounded up to 64; a quarter of an f32 gallery), one int8 per element and one f32 scale per row
+        (include/clipgpu.h has the rule).  The rows present are coded now; ``add``, ``add_device`` and
+        ``set_rows`` keep the codes current from here on, ``clear`` keeps them enabled.  A second call is a
+        no-op.  E <= 1024."""
+        if self.E > CODES_MAX_E:
+            raise ValueError(f"codes need E <= {CODES_MAX_E}, got {self.E}")
+        check(lib().clipgpu_index_enable_codes(self.handle))
+
+    @property
+    def has_codes(self) -> bool:
+        return bool(lib().clipgpu_index_has_codes(self.handle))
+
+    def drop_codes(self) -> None:
+        """Frees the codes; ``search_coded`` raises until ``enable_codes`` is called again."""
+        check(lib().clipgpu_index_drop_codes(self.handle))
+
+    def codes(self, first: int = 0, n=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The codes of rows [first, first + n) (n = None: to the end): (int8 [n, E], scales f32 [n])."""
+        n = len(self) - int(first) if n is None else int(n)
+        out = np.empty((max(n, 0), self.E), np.int8)
+        scales = np.empty(max(n, 0), np.float32)
+        check(lib().clipgpu_index_get_codes(self.handle, int(first), n, out.ctypes.data, scales.ctypes.data))
+        return out, scales
+
+    @staticmethod
+    def _coded_args(k, refine) -> Tuple[int, int]:
+        """(k, refine), checked before any native call; refine None = min(128, max(32, 4 k))."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"k must be an integer, got {type(k).__name__}")
+        if not 1 <= int(k) <= TOPK_MAX:
+            raise ValueError(f"k must be in 1..{TOPK_MAX}, got {int(k)}")
+        if refine is None:
+            refine = min(TOPK_MAX, max(32, 4 * int(k)))
+        if isinstance(refine, bool) or not isinstance(refine, (int, np.integer)):
+            raise TypeError(f"refine must be an integer, got {type(refine).__name__}")
+        if not int(k) <= int(refine) <= TOPK_MAX:
+            raise ValueError(f"refine must be in k..{TOPK_MAX}, got {int(refine)} with k = {int(k)}")
+        return int(k), int(refine)
+
+    def search_coded(self, queries, k: int, refine=None, logit_scale: float = 1.0, logit_bias: float = 0.0,
+                     allow=None, return_candidates: bool = False):
+        """``search`` in two stages: a coarse scan of the int8 codes picks ``refine`` candidate rows per query
+        (by the integer dot product of the codes times the row's scale, equal ones to the lower row), and the
+        candidates are re-ranked exactly.  Per query the result is -- ids, order and score bits -- what
+        ``search(query, k, ..., allow=mask)`` returns with ``mask`` = its candidates: a row the coarse stage
+        misses is never found, and that is the whole approximation.  With at most ``refine`` live allowed rows
+        it is ``search`` itself.  1 <= k <= refine <= 128; ``refine=None`` is min(128, max(32, 4 k)).
+        ``return_candidates=True`` adds (candidates int64 [nq, refine], -1 padded, and their coarse scores f32
+        [nq, refine], -inf padded), best first.  Raises if the index has no codes."""
+        k, refine = self._coded_args(k, refine)
+        words = self._allow_words(allow)
+        q = self._rows(queries, "queries")
+        idx = np.empty((q.shape[0], k), np.int64)
+        score = np.empty((q.shape[0], k), np.float32)
+        cand = np.empty((q.shape[0], refine), np.int64) if return_candidates else None
+        coarse = np.empty((q.shape[0], refine), np.float32) if return_candidates else None
+        check(lib().clipgpu_index_search_coded(self.handle, q.ctypes.data, q.shape[0], k, refine, float(logit_scale),
+                                               float(logit_bias), None if words is None else words.ctypes.data,
+                                               idx.ctypes.data, score.ctypes.data,
+                                               None if cand is None else cand.ctypes.data,
+                                               None if coarse is None else coarse.ctypes.data))
+        return (idx, score, cand, coarse) if return_candidates else (idx, score)
+
+    def search_coded_device(self, d_queries: int, nq: int, k: int, d_idx: int, d_score: int, refine=None,
+                            logit_scale: float = 1.0, logit_bias: float = 0.0, stream: int = 0, d_allow: int = 0,
+                            d_cand: int = 0, d_coarse: int = 0) -> None:
+        """``search_coded`` on device pointers (as ``search_device``; ``d_cand`` int64 [nq, refine] and
+        ``d_coarse`` f32 [nq, refine] out, or 0 = not wanted), ordered on ``stream``; returns without
+        synchronising."""
+        k, refine = self._coded_args(k, refine)
+        check(lib().clipgpu_index_search_coded_device(self.handle, c_void_p(d_queries), int(nq), k, refine,
+                                                      float(logit_scale), float(logit_bias),
+                                                      c_void_p(d_allow or None), c_void_p(d_idx), c_void_p(d_score),
+                                                      c_void_p(d_cand or None), c_void_p(d_coarse or None),
+                                                      c_void_p(stream or None)))

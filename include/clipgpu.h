@@ -521,6 +521,39 @@ int clipgpu_index_search_probed_device(clipgpu_index* ix, const float* d_queries
                                        int64_t nprobe, float logit_scale, float logit_bias, const uint32_t* d_allow,
                                        int64_t* d_idx, float* d_score, int64_t* d_probes, void* stream);
 
+/* ---- int8 codes and the coded search: a coarse scan of a compressed copy, then an exact re-rank ----------
+ * clipgpu_index_enable_codes allocates, beside the gallery, int8 codes [capacity][Ep] (Ep = E rounded up to 64,
+ * the bytes past E zero) and one f32 scale per row -- capacity * (Ep + 4) bytes, a quarter of an f32 gallery --
+ * and codes rows [0, size).  From then on add, add_device and set_rows code the rows they write (same stream,
+ * after the gallery write); clear keeps the codes enabled; remove needs nothing.  Enabling twice is a no-op;
+ * drop_codes frees them.  E > 1024 is refused.  The code of a row x, as stored and widened to f32 (a 16-bit
+ * index codes its rounded rows), every step one f32 operation:
+ *   m = max |x_i|;  if m is not finite (an inf or a NaN anywhere in the row), m == 0 or 127 / m is not finite:
+ *   every code 0 and scale 0;  else inv = 127 / m, code_i = clamp(rint(x_i * inv), -127, 127) with rint to
+ *   nearest even, scale = m / 127 (both divisions correctly rounded).
+ * get_codes copies rows [first, first + n) out: out_codes int8 [n][E], out_scales f32 [n].
+ *
+ * clipgpu_index_search_coded: the queries are coded by the same rule; for query q and live allowed row j
+ *   coarse[q][j] = (float)(sum_i cq_i * cg_i) * scale[j]     (an exact int32 sum, one f32 multiply),
+ * negated when logit_scale < 0 (0 counts as positive).  The candidates of q are the `refine` rows with the
+ * largest (coarse, then lower row) in the search's order; the result is, bit for bit -- ids, order, score bits,
+ * (-1, -inf) padding -- what clipgpu_index_search_filtered returns with allow = those candidates: approximate
+ * only in which rows reach the exact re-rank.  If at most `refine` rows are live and allowed it is the plain
+ * search.  1 <= k <= refine <= CLIPGPU_TOPK_MAX.  out_cand (int64 [nq][refine], -1 padded) and out_coarse (f32
+ * [nq][refine], -inf padded) receive the candidates and their coarse scores, best first, or are NULL.
+ * Refused before any device call: a NULL argument, an empty batch, k or refine out of range, an index without
+ * codes.  The device form never synchronises and is ordered like clipgpu_index_search_probed_device. */
+int clipgpu_index_enable_codes(clipgpu_index* ix);
+int clipgpu_index_has_codes(const clipgpu_index* ix);
+int clipgpu_index_drop_codes(clipgpu_index* ix);
+int clipgpu_index_get_codes(clipgpu_index* ix, int64_t first, int64_t n, int8_t* out_codes, float* out_scales);
+int clipgpu_index_search_coded(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, int64_t refine,
+                               float logit_scale, float logit_bias, const uint32_t* allow, int64_t* out_idx,
+                               float* out_score, int64_t* out_cand, float* out_coarse);
+int clipgpu_index_search_coded_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k,
+                                      int64_t refine, float logit_scale, float logit_bias, const uint32_t* d_allow,
+                                      int64_t* d_idx, float* d_score, int64_t* d_cand, float* d_coarse, void* stream);
+
 /* ---- data-parallel sharding + the RCCL all-gather (north_star: "batches shard
  * data-parallel across the 8 GPUs of one node with an RCCL all-gather over xGMI only for the final
  * embedding matrix").  The reference has no multi-device path: embed_images / embed_texts

@@ -303,6 +303,11 @@ int clipgpu_test_probe_parts(int parts);
 /* The most query rows of one probed launch (0 = the default, as many as the workspace holds, at most 256), as
  * above: small inputs then run several chunks.  The result never depends on it. */
 int clipgpu_test_probe_chunk(int rows);
+/* The stages a coded search runs (clipgpu_index_search_coded[_device]), process-wide and atomic, for timing them
+ * apart: 0 = both (the default), 1 = the coarse stage only (the queries' codes, the scan, the candidates' merge;
+ * the results are not written), 2 = the re-rank only, on the candidates the last coarse stage left in the handle
+ * (meaningful for the same queries, at most 256 of them). */
+int clipgpu_test_codes_stage(int stage);
 
 #ifdef __cplusplus
 }

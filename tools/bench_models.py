@@ -533,6 +533,88 @@ def ivf_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Cs=(256, 1024, 4096), npro
         assert verdict[0] < verdict[1], f"probed max {verdict[0]} ms is not below plain min {verdict[1]} ms"
 
 
+def codes_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 16, 256), refines=(32, 128), centres=1024, sigma=0.05):
+    """The coded search (int8 coarse scan + exact re-rank) against the plain search on the ivf leg's clustered f32
+    gallery.  Per Q, legs alternating in one process (rotating order, device-event timings after `warmup` rounds):
+    search_device -- unchanged code, the yardstick measured in the same process -- and per refine
+    search_coded_device whole, its coarse stage alone (the queries' codes, the scan, the candidates' merge) and its
+    re-rank alone (clipgpu_test_codes_stage 1 and 2; the re-rank runs on the candidates the coarse leg before it
+    left).  Beside each: recall@k against the plain search (a property of the data, reported, not a bar).  One-off:
+    the time of enable_codes (wall clock, synchronised; allocation + coding 2^20 rows).  The one timing condition:
+    at Q = 256, refine = 128 the coded [min, max] lies wholly below the plain [min, max]; asserted after the lines
+    are printed."""
+    from open_clip_inference import EmbeddingIndex, _lib
+    torch.manual_seed(0)
+    s = torch.cuda.current_stream().cuda_stream
+    cen0 = torch.nn.functional.normalize(torch.randn(centres, E, device="cuda"), dim=1)
+
+    def draw(n):
+        return torch.nn.functional.normalize(cen0[torch.randint(0, centres, (n,), device="cuda")] +
+                                             sigma * torch.randn(n, E, device="cuda"), dim=1).contiguous()
+
+    def stage(v):
+        _lib.check(_lib.lib().clipgpu_test_codes_stage(v))
+
+    g = draw(N)
+    qs = {Q: draw(Q) for Q in Qs}
+    verdict = None
+    with EmbeddingIndex(E, N) as ix:
+        ix.add_device(g.data_ptr(), N, s)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ix.enable_codes()
+        ix.codes(0, 1)  # waits for the coding
+        print(json.dumps({"measure": "codes_enable", "N": N, "E": E, "enable_codes_wall_ms": round((time.perf_counter() - t0) * 1e3, 2),
+                          "codes_bytes": N * (E + 4)}), flush=True)
+        for Q in Qs:
+            q = qs[Q]
+            names = ["plain"] + [f"{w}{r}" for r in refines for w in ("coded", "coarse", "rerank")]
+            res = {n: (torch.empty((Q, k), dtype=torch.int64, device="cuda"), torch.empty((Q, k), device="cuda"))
+                   for n in names}
+
+            def plain():
+                ix.search_device(q.data_ptr(), Q, k, res["plain"][0].data_ptr(), res["plain"][1].data_ptr(), 100.0, 0.0, s)
+
+            def coded(name, r, st):
+                def fn():
+                    stage(st)
+                    try:
+                        ix.search_coded_device(q.data_ptr(), Q, k, res[name][0].data_ptr(), res[name][1].data_ptr(), r,
+                                               100.0, 0.0, s)
+                    finally:
+                        stage(0)
+                return fn
+
+            # the three legs of a refine stay together and in this order: the re-rank needs the coarse leg's candidates
+            groups = [[("plain", plain)]] + [[(f"coded{r}", coded(f"coded{r}", r, 0)), (f"coarse{r}", coded(f"coarse{r}", r, 1)),
+                                              (f"rerank{r}", coded(f"rerank{r}", r, 2))] for r in refines]
+            ms = {n: [] for n in names}
+            for rnd in range(warmup + runs):
+                r0 = rnd % len(groups)
+                for grp in groups[r0:] + groups[:r0]:
+                    for name, fn in grp:
+                        t = _event_ms(fn)
+                        if rnd >= warmup:
+                            ms[name].append(t)
+            want = res["plain"][0].cpu().numpy()
+            out = {"measure": "codes_search", "N": N, "E": E, "Q": Q, "k": k, "runs": runs, "plain": _stats(ms["plain"], N * E * 4)}
+            for r in refines:
+                got = res[f"coded{r}"][0].cpu().numpy()
+                recall = float(np.mean([len(set(a) & set(b)) for a, b in zip(got.tolist(), want.tolist())])) / k
+                st = _stats(ms[f"coded{r}"], N * (E + 4))
+                st["codes_TBps"] = st.pop("gallery_TBps")
+                for w in ("coarse", "rerank"):
+                    v = ms[f"{w}{r}"]
+                    st[w] = {"ms_median": round(float(np.median(v)), 3), "ms_min_max": [round(min(v), 3), round(max(v), 3)]}
+                st.update({f"recall_at_{k}": round(recall, 4), "plain_over_coded": round(out["plain"]["ms_median"] / st["ms_median"], 2)})
+                out[f"refine{r}"] = st
+            print(json.dumps(out), flush=True)
+            if Q == 256 and 128 in refines:
+                verdict = (max(ms["coded128"]), min(ms["plain"]))
+    if verdict is not None:
+        assert verdict[0] < verdict[1], f"coded max {verdict[0]} ms is not below plain min {verdict[1]} ms"
+
+
 def topk_routes_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 2, 4, 8, 12, 16)):
     """The measurement kNarrowRows (csrc/kernels/kernels.hpp) is set by: for every query count the
     few-query kernel can take, that kernel (route 2) against the wide one (route 1) on an f32 gallery,
@@ -765,6 +847,8 @@ if __name__ == "__main__":
         kmeans_leg()
     if "ivf" in which:  # the probed search against the plain search on a clustered gallery
         ivf_leg()
+    if "codes" in which:  # the coded search (int8 scan + exact re-rank) against the plain search
+        codes_leg()
     if "so400m" in which:
         device_leg("so400m_vision", SO400M_16_SIGLIP2_384_CFG, 0, 128)
     if "h14" in which:
