@@ -6,11 +6,18 @@ namespace clipgpu {
 
 namespace {
 
-// Caller-registered host ranges (clipgpu_host_register): process-wide, hipHostRegister'ed.
+// Caller-registered host ranges (clipgpu_host_register): process-wide.  A range inside an allocation of
+// clipgpu_host_alloc is pinned already; any other is hipHostRegister'ed (`pinned_here`).
 constexpr size_t kHostPage = 4096;
+struct HostRange {
+  uintptr_t first;  // base
+  size_t second;    // bytes
+  bool pinned_here;
+};
 struct HostRanges {
   std::mutex mu;
-  std::vector<std::pair<uintptr_t, size_t>> r;  // (base, bytes)
+  std::vector<HostRange> r;
+  std::vector<std::pair<uintptr_t, size_t>> alloc;  // clipgpu_host_alloc's (base, bytes): whole pages
 };
 HostRanges& host_ranges() {
   static HostRanges h;
@@ -24,6 +31,18 @@ bool host_registered(const void* p, size_t n) {
   for (const auto& rg : h.r)
     if (a >= rg.first && a + n <= rg.first + rg.second) return true;
   return false;
+}
+// Waits for every device's queued work (before host memory is unpinned or freed under it).
+void sync_all_devices() {
+  int ndev = 0;
+  HIP_CHECK(hipGetDeviceCount(&ndev));
+  int cur = 0;
+  HIP_CHECK(hipGetDevice(&cur));
+  for (int d = 0; d < ndev; ++d) {
+    HIP_CHECK(hipSetDevice(d));
+    HIP_CHECK(hipDeviceSynchronize());
+  }
+  HIP_CHECK(hipSetDevice(cur));
 }
 
 // The fixed partition of a round's max_batch rows into host-path chunks: part[0] = 0 < part[1] <
@@ -434,8 +453,19 @@ int clipgpu_host_register(void* ptr, size_t bytes) {
         throw ClipErr(CLIPGPU_ERR_INVALID,
                       "host range shares a memory page with a registered one (registration pins whole pages): "
                       "register page-aligned buffers");
-    HIP_CHECK(hipHostRegister(ptr, bytes, hipHostRegisterMapped | hipHostRegisterPortable));  // every device
-    h.r.emplace_back(a, bytes);
+    // memory of clipgpu_host_alloc is pinned for every device already (and cannot be registered again)
+    bool pinned = false;
+    for (const auto& al : h.alloc) pinned = pinned || (a >= al.first && a + bytes <= al.first + al.second);
+    if (!pinned) {
+      const hipError_t err = hipHostRegister(ptr, bytes, hipHostRegisterMapped | hipHostRegisterPortable);
+      if (err != hipSuccess) {
+        (void)hipGetLastError();  // reported here (hip_check.hpp)
+        throw ClipErr(CLIPGPU_ERR_DEVICE, std::string("HIP error: ") + hipGetErrorString(err) +
+                                              " (hipHostRegister: where the platform cannot pin memory that the "
+                                              "process already has, allocate the buffer with clipgpu_host_alloc)");
+      }
+    }
+    h.r.push_back(HostRange{a, bytes, !pinned});
   });
 }
 
@@ -445,21 +475,47 @@ int clipgpu_host_unregister(void* ptr) {
     std::lock_guard<std::mutex> lk(h.mu);
     for (size_t i = 0; i < h.r.size(); ++i)
       if (h.r[i].first == (uintptr_t)ptr) {
-        // no transfer of any device may still reference the range
-        int ndev = 0;
-        HIP_CHECK(hipGetDeviceCount(&ndev));
-        int cur = 0;
-        HIP_CHECK(hipGetDevice(&cur));
-        for (int d = 0; d < ndev; ++d) {
-          HIP_CHECK(hipSetDevice(d));
-          HIP_CHECK(hipDeviceSynchronize());
-        }
-        HIP_CHECK(hipSetDevice(cur));
-        HIP_CHECK(hipHostUnregister(ptr));
+        sync_all_devices();  // no transfer of any device may still reference the range
+        if (h.r[i].pinned_here) HIP_CHECK(hipHostUnregister(ptr));
         h.r.erase(h.r.begin() + (long)i);
         return;
       }
     throw ClipErr(CLIPGPU_ERR_INVALID, "host range not registered");
+  });
+}
+
+int clipgpu_host_alloc(size_t bytes, void** ptr) {
+  return guarded([&]() {
+    if (!ptr) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL buffer");
+    *ptr = nullptr;
+    if (bytes == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL / empty host range");
+    // whole pages, so that no two allocations (hence no two registered buffers) share one
+    const size_t whole = (bytes + kHostPage - 1) / kHostPage * kHostPage;
+    void* p = nullptr;
+    HIP_CHECK(hipHostMalloc(&p, whole, hipHostMallocMapped | hipHostMallocPortable));  // every device
+    HostRanges& h = host_ranges();
+    std::lock_guard<std::mutex> lk(h.mu);
+    h.alloc.emplace_back((uintptr_t)p, whole);
+    *ptr = p;
+  });
+}
+
+int clipgpu_host_free(void* ptr) {
+  return guarded([&]() {
+    HostRanges& h = host_ranges();
+    std::lock_guard<std::mutex> lk(h.mu);
+    for (size_t i = 0; i < h.alloc.size(); ++i)
+      if (h.alloc[i].first == (uintptr_t)ptr) {
+        const uintptr_t end = h.alloc[i].first + h.alloc[i].second;
+        for (const auto& rg : h.r)
+          if (rg.first >= h.alloc[i].first && rg.first < end)
+            throw ClipErr(CLIPGPU_ERR_INVALID, "host allocation holds a registered range: unregister it first");
+        sync_all_devices();
+        HIP_CHECK(hipHostFree(ptr));
+        h.alloc.erase(h.alloc.begin() + (long)i);
+        return;
+      }
+    throw ClipErr(CLIPGPU_ERR_INVALID, "not a clipgpu_host_alloc allocation");
   });
 }
 

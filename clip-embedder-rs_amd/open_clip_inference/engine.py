@@ -265,16 +265,34 @@ def profile_read(engine: "Engine", category: str):
     return ms.value, n.value
 
 
+class _HostBlock:
+    """Pinned host memory of clipgpu_host_alloc, freed with the last array over it."""
+
+    def __init__(self, nbytes: int):
+        p = c_void_p()
+        check(lib().clipgpu_host_alloc(nbytes, ctypes.byref(p)))
+        self._p, self._n = p.value, nbytes
+
+    @property
+    def __array_interface__(self):
+        return {"shape": (self._n,), "typestr": "|u1", "data": (self._p, False), "version": 3}
+
+    def __del__(self):
+        try:  # refused while a range of it is still registered: the memory then stays allocated
+            lib().clipgpu_host_free(self._p)
+        except Exception:
+            pass
+
+
 def host_buffer(shape, dtype) -> np.ndarray:
     """An empty C-contiguous host array that owns whole memory pages (page-aligned start, no other
     allocation on its last page): what host_register needs, since registration pins whole pages and two
-    registered ranges may not share one (clipgpu_host_register)."""
+    registered ranges may not share one (clipgpu_host_register).  The memory is allocated pinned
+    (clipgpu_host_alloc), so registering it works also where memory the process already has cannot
+    be pinned; it is freed with the last array that views it."""
     dtype = np.dtype(dtype)
     n = int(np.prod(shape, dtype=np.int64)) * dtype.itemsize
-    page = 4096
-    raw = np.empty(((n + page - 1) // page + 1) * page, np.uint8)
-    off = (-raw.ctypes.data) % page
-    return raw[off:off + n].view(dtype).reshape(shape)
+    return np.asarray(_HostBlock(max(n, 1)))[:n].view(dtype).reshape(shape)
 
 
 def host_register(arr: np.ndarray) -> None:

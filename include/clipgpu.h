@@ -161,9 +161,17 @@ int clipgpu_embed_u8(clipgpu_engine* e, const uint8_t* nhwc, int64_t B, int64_t 
  * registered range then DMAs straight from (into) it, skipping the host copy; the batch still moves
  * in one chunk per lane, so the first chunk's transfer is what is exposed before the forward starts.
  * Results are bit-identical either way.  Process-wide; the caller keeps the memory alive, and
- * unregisters it only when no embed_* call is using it, before freeing it.  Ranges may not overlap. */
+ * unregisters it only when no embed_* call is using it, before freeing it.  Ranges may not overlap.
+ *
+ * Some platforms (virtual machines among them) cannot pin memory that the process already has: there
+ * hipHostRegister, and so clipgpu_host_register of such memory, fails.  clipgpu_host_alloc returns
+ * memory allocated pinned (hipHostMalloc, mapped and portable; whole pages of its own), which works
+ * everywhere: a range inside it registers without being pinned again, and is then used in the same
+ * way.  clipgpu_host_free takes the pointer clipgpu_host_alloc gave, after its ranges are unregistered. */
 int clipgpu_host_register(void* ptr, size_t bytes);
 int clipgpu_host_unregister(void* ptr);
+int clipgpu_host_alloc(size_t bytes, void** ptr);
+int clipgpu_host_free(void* ptr);
 
 /* ---- text forward ---------------------------------------------------------------------
  * Replaces session.run(input_ids [, attention_mask]) in TextEmbedder::embed_texts

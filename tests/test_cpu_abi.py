@@ -331,6 +331,23 @@ def test_host_register_argument_errors():
         _lib.check(_lib.lib().clipgpu_host_unregister(buf.ctypes.data))
 
 
+def test_host_alloc_argument_errors():
+    """clipgpu_host_alloc / _free refuse a NULL result pointer, an empty allocation and a pointer that
+    clipgpu_host_alloc did not give, before touching HIP (the allocation needs a GPU:
+    tests/test_gpu_api.py)."""
+    from open_clip_inference import _lib
+    from open_clip_inference.error import ClipError
+    buf = np.zeros(64, np.uint8)
+    p = ctypes.c_void_p(1)
+    with pytest.raises(ClipError, match="NULL buffer"):
+        _lib.check(_lib.lib().clipgpu_host_alloc(64, None))
+    with pytest.raises(ClipError, match="NULL / empty"):
+        _lib.check(_lib.lib().clipgpu_host_alloc(0, ctypes.byref(p)))
+    assert p.value is None
+    with pytest.raises(ClipError, match="not a clipgpu_host_alloc"):
+        _lib.check(_lib.lib().clipgpu_host_free(buf.ctypes.data))
+
+
 def test_facade_math_loads_without_hip():
     """Clip.softmax / Clip.sigmoid (host math in the reference, src/clip.rs:172-185) run from the
     host-only library (no HIP, no RCCL in its dependencies), bit-exact to the main library."""

@@ -340,9 +340,10 @@ def test_multi_round_host_calls_alternate_buffer_sets_bit_exactly():
         for registered, flags in ((False, 1), (True, 1)):
             _lib.check(_lib.lib().clipgpu_test_host_plan(e.handle, 0, no_bounds, flags))
             from open_clip_inference.engine import host_buffer
-            xin = host_buffer(x.shape, x.dtype)
+            # host_buffer's memory is pinned: the pageable case takes plain numpy arrays
+            xin = host_buffer(x.shape, x.dtype) if registered else np.empty_like(x)
             xin[...] = x
-            out = host_buffer((B, 512), np.float32)
+            out = host_buffer((B, 512), np.float32) if registered else np.empty((B, 512), np.float32)
             if registered:
                 host_register(xin)
                 host_register(out)
@@ -357,6 +358,53 @@ def test_multi_round_host_calls_alternate_buffer_sets_bit_exactly():
                     host_unregister(out)
     ve.close()
     te.close()
+
+
+def test_host_alloc_owns_pages_and_refuses_a_free_under_a_registration():
+    """clipgpu_host_alloc gives page-aligned pinned memory in whole pages of its own (two small
+    allocations never share a page), a range inside it registers (it is pinned already) and
+    unregisters, clipgpu_host_free is refused while such a range is registered and a second time,
+    and host_buffer's arrays lie in such memory and free it with their last view."""
+    import ctypes
+    import gc
+    from open_clip_inference import _lib
+    from open_clip_inference.engine import host_buffer, host_register, host_unregister
+    from open_clip_inference.error import ClipError
+    L = _lib.lib()
+    p, q = ctypes.c_void_p(), ctypes.c_void_p()
+    _lib.check(L.clipgpu_host_alloc(100, ctypes.byref(p)))
+    _lib.check(L.clipgpu_host_alloc(100, ctypes.byref(q)))
+    assert p.value % 4096 == 0 and q.value % 4096 == 0 and abs(p.value - q.value) >= 4096
+    mem = np.frombuffer((ctypes.c_uint8 * 4096).from_address(p.value), np.uint8)  # the whole page is ours
+    mem[:] = 7
+    _lib.check(L.clipgpu_host_register(p.value + 8, 64))
+    with pytest.raises(ClipError, match="holds a registered range"):
+        _lib.check(L.clipgpu_host_free(p))
+    _lib.check(L.clipgpu_host_unregister(p.value + 8))
+    del mem
+    _lib.check(L.clipgpu_host_free(p))
+    with pytest.raises(ClipError, match="not a clipgpu_host_alloc"):
+        _lib.check(L.clipgpu_host_free(p))
+    _lib.check(L.clipgpu_host_free(q))
+    a = host_buffer((3, 5), np.float32)
+    assert a.shape == (3, 5) and a.dtype == np.float32 and a.flags["C_CONTIGUOUS"] and a.ctypes.data % 4096 == 0
+    addr = a.ctypes.data
+    row = a[1]
+    host_register(a)
+    host_unregister(a)
+    del a
+    gc.collect()
+    row[:] = 1.0  # a view keeps the memory
+    with pytest.raises(ClipError, match="holds a registered range"):
+        host_register(row)
+        try:
+            _lib.check(L.clipgpu_host_free(addr))
+        finally:
+            host_unregister(row)
+    del row
+    gc.collect()
+    with pytest.raises(ClipError, match="not a clipgpu_host_alloc"):  # freed with the last view
+        _lib.check(L.clipgpu_host_free(addr))
 
 
 def test_one_device_clique_runs_the_multi_device_comm_path():
