@@ -46,6 +46,11 @@
 // of queries: the queries' codes, the coarse scan of the gallery's codes and the search's merge with k = refine
 // (the candidates), then the probe kernel over each query's candidates as a list of its own and the merge again.
 // An index whose codes were never enabled runs none of this.
+//
+// Deep search (clipgpu_index_search_deep[_device]; kernels/deep.hip): the search for k up to 4096.  The same
+// chunks, route and span cut as a search; per chunk launch_deep enqueues its fixed sequence of launches into a
+// work area of the handle's (the chunk's histograms, state and candidate records, and the host form's staged
+// results), allocated at the first deep search and kept until the handle is destroyed.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -131,6 +136,7 @@ struct clipgpu_index {
   float* cd_scale = nullptr;     // [capacity]
   char* cd_work = nullptr;       // a coded search in flight: the regions carve_codes places
   int64_t cd_Ep = 0;
+  char* dp_work = nullptr;       // the deep search: what deep_buffers carves; lazy, kept until the handle is destroyed
   hipStream_t stream = nullptr;  // the host-buffer forms' stream
   hipEvent_t done = nullptr;     // recorded after every device-side operation
 };
@@ -694,9 +700,102 @@ int coded_host(clipgpu_index* ix, const CodedReq& r, const CodedOut& o) {
   });
 }
 
+// ---- deep search (kernels/deep.hip) -----------------------------------------------------------------------
+// One call, as SearchReq / SearchOut; passes: int32 [nq] or NULL.
+struct DeepReq { const float* q; int64_t nq, k; float scale, bias; const uint32_t* allow; };
+struct DeepOut { int64_t* idx; float* score; int32_t* passes; };
+
+// The refusals that need no lock; then as enter_search.
+std::unique_lock<std::mutex> enter_deep(clipgpu_index* ix, const DeepReq& r, const DeepOut& o) {
+  if (!ix || !r.q || !o.idx || !o.score) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+  if (r.nq <= 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
+  if (r.k < 1 || r.k > CLIPGPU_DEEP_K_MAX)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "k must be in 1.." + std::to_string(CLIPGPU_DEEP_K_MAX) + ", got " +
+                                           std::to_string(r.k));
+  std::unique_lock<std::mutex> lk(ix->mu);
+  if (ix->size == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");  // an empty gallery
+  HIP_CHECK(hipSetDevice(ix->device));
+  return lk;
+}
+
+// The deep search's work area: the chunk's device state (deep_carve) and, behind it, the host form's staged
+// indices, scores and pass counts (`st`).  Allocated at the first deep search; a failed allocation is
+// CLIPGPU_ERR_DEVICE and leaves the handle without the area, usable.  Callers hold the mutex.
+DeepWork deep_buffers(clipgpu_index* ix, DeepOut* st) {
+  DeepWork w;
+  size_t off = deep_carve(nullptr, &w);
+  const size_t slots = (size_t)kDeepChunk * kDeepKMax;
+  off += align256(slots * 8) + align256(slots * 4) + align256((size_t)kDeepChunk * 4);
+  if (!ix->dp_work) HIP_CHECK(hipMalloc((void**)&ix->dp_work, off));
+  off = deep_carve(ix->dp_work, &w);
+  st->idx = carve<int64_t>(ix->dp_work, off, slots * 8);
+  st->score = carve<float>(ix->dp_work, off, slots * 4);
+  st->passes = carve<int32_t>(ix->dp_work, off, (size_t)kDeepChunk * 4);
+  return w;
+}
+
+// Searches the device rows r.q in chunks of kQueryChunk rows on `s`, all under one mask, into the device
+// buffers of `o`: per chunk the fixed launch sequence of launch_deep, nothing read back.
+void deep_on(clipgpu_index* ix, const DeepReq& r, const uint32_t* mask, const DeepWork& w, const DeepOut& o,
+             hipStream_t s) {
+  static_assert(kQueryChunk == kDeepChunk, "a chunk's state holds kDeepChunk queries");
+  for (int64_t q0 = 0; q0 < r.nq; q0 += kQueryChunk) {
+    const int rows = (int)std::min(kQueryChunk, r.nq - q0);
+    const TopkPlan p = topk_plan(ix->size, rows, ix->ws_blocks);  // the search's route and span cut
+    HIP_CHECK(launch_deep({r.q + q0 * ix->E, rows, ix->gallery, ix->dtype, (int)ix->size, (int)ix->E, r.scale, r.bias,
+                           (int)r.k, p, mask, w, o.idx + q0 * r.k, o.score + q0 * r.k,
+                           o.passes ? o.passes + q0 : nullptr, s}));
+  }
+  mark_last(ix, s);
+}
+
+int deep_device(clipgpu_index* ix, const DeepReq& r, const DeepOut& o, hipStream_t s) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_deep(ix, r, o);
+    DeepOut st;
+    const DeepWork w = deep_buffers(ix, &st);
+    order_after_last(ix, s);
+    deep_on(ix, r, build_mask(ix, r.allow, s), w, o, s);
+  });
+}
+
+int deep_host(clipgpu_index* ix, const DeepReq& r, const DeepOut& o) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_deep(ix, r, o);
+    HIP_CHECK(hipEventSynchronize(ix->done));  // the staging buffers and the filter area are free
+    DeepOut st;
+    const DeepWork w = deep_buffers(ix, &st);
+    if (r.allow) HIP_CHECK(copy_h2d(ix->d_eff, r.allow, (size_t)live_words(ix->size) * 4));
+    const uint32_t* mask = build_mask(ix, r.allow ? ix->d_eff : nullptr, ix->stream);
+    if (!o.passes) st.passes = nullptr;
+    for (int64_t q0 = 0; q0 < r.nq; q0 += kQueryChunk) {
+      const DeepReq c = {ix->st_q, std::min(kQueryChunk, r.nq - q0), r.k, r.scale, r.bias, nullptr};
+      HIP_CHECK(copy_h2d(ix->st_q, r.q + q0 * ix->E, (size_t)c.nq * ix->E * 4));
+      deep_on(ix, c, mask, w, st, ix->stream);
+      HIP_CHECK(hipStreamSynchronize(ix->stream));
+      HIP_CHECK(copy_d2h(o.idx + q0 * r.k, st.idx, (size_t)c.nq * r.k * 8));
+      HIP_CHECK(copy_d2h(o.score + q0 * r.k, st.score, (size_t)c.nq * r.k * 4));
+      if (st.passes) HIP_CHECK(copy_d2h(o.passes + q0, st.passes, (size_t)c.nq * 4));
+    }
+  });
+}
+
 }  // namespace
 
 extern "C" {
+
+int clipgpu_index_search_deep(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, float logit_scale,
+                              float logit_bias, const uint32_t* allow, int64_t* out_idx, float* out_score,
+                              int32_t* out_passes) {
+  return deep_host(ix, {queries, nq, k, logit_scale, logit_bias, allow}, {out_idx, out_score, out_passes});
+}
+
+int clipgpu_index_search_deep_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k,
+                                     float logit_scale, float logit_bias, const uint32_t* d_allow, int64_t* d_idx,
+                                     float* d_score, int32_t* d_passes, void* stream) {
+  return deep_device(ix, {d_queries, nq, k, logit_scale, logit_bias, d_allow}, {d_idx, d_score, d_passes},
+                     (hipStream_t)stream);
+}
 
 int clipgpu_index_partition(clipgpu_index* ix, const float* centroids, int64_t C, int64_t* out_counts) {
   return guarded([&]() {
@@ -1010,6 +1109,7 @@ void clipgpu_index_destroy(clipgpu_index* ix) {
   if (ix->cd_codes) (void)hipFree(ix->cd_codes);
   if (ix->cd_scale) (void)hipFree(ix->cd_scale);
   if (ix->cd_work) (void)hipFree(ix->cd_work);
+  if (ix->dp_work) (void)hipFree(ix->dp_work);
   if (ix->work) (void)hipFree(ix->work);
   if (ix->gallery) (void)hipFree(ix->gallery);
   delete ix;

@@ -359,6 +359,48 @@ struct RangeArgs {
 };
 hipError_t launch_range(const RangeArgs& a);
 
+// Deep top-k search (kernels/deep.hip): per query row the first k rows of launch_topk's order for
+// 1 <= k <= kDeepKMax, by a radix select on topk_key (8 histogram passes of range.hip's two loops at most), an
+// emission of every key at or above the k-th and a sort.  out_idx / out_score [nq][k] as launch_topk writes
+// them (scores with its bits; (-1, -inf) beyond the live allowed rows); out_passes (NULL = not wanted) int32
+// [nq], the histogram passes each query needed.  One call is one chunk of nq <= kDeepChunk query rows (the wide
+// kernels, or the few-query ones when plan.narrow; the plan is topk_plan(N, nq, ...)) and enqueues a fixed
+// sequence of launches that reads nothing back.  mask as in TopkArgs.
+constexpr int kDeepKMax = 4096;
+constexpr int kDeepChunk = 256;
+constexpr int kDeepCandMax = 8192;  // candidate records per query: the default capacity and the most
+// The candidate capacity of a search for k: max(k, g_deep_cand or kDeepCandMax) (clipgpu_test_deep_cand; 0 = off).
+extern std::atomic<int> g_deep_cand;
+int deep_cand(int k);
+// A chunk's device state; deep_carve places it at `base` (256-byte aligned; NULL: nowhere) and returns its bytes.
+struct DeepWork {
+  unsigned* hist;              // [kDeepChunk][256]: the bins of the pass in flight
+  unsigned long long* prefix;  // [kDeepChunk]: the key digits fixed so far, zeros below
+  unsigned* above;             // the keys strictly above the prefix's bucket
+  int* done;
+  unsigned* count;             // the emit pass's slot counters, one per 128 bytes
+  int* passes;
+  unsigned long long* rec_key;  // [kDeepChunk][capacity]: a candidate's key
+  unsigned* rec_bits;           // and its score's bits
+};
+size_t deep_carve(char* base, DeepWork* w);
+struct DeepArgs {
+  const float* q;  // [nq][E]
+  int nq;
+  const void* g;  // [N][E] of dtype (TopkGal)
+  int dtype, N, E;
+  float scale, bias;
+  int k;
+  TopkPlan plan;
+  const uint32_t* mask;
+  DeepWork work;
+  int64_t* out_idx;
+  float* out_score;
+  int32_t* out_passes;
+  hipStream_t stream;
+};
+hipError_t launch_deep(const DeepArgs& a);
+
 // Assignment (kernels/cluster.hip): for every gallery row j < N the centroid with the largest
 // topk_key(score, centroid index), score = fmaf(dot(c, g[j]), scale, bias) with launch_topk's bits:
 // label[j] (int32) and score[j]; a row that mask (as in TopkArgs) does not allow gets (-1, -inf).  c: f32

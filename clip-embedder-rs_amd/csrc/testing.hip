@@ -414,6 +414,14 @@ int clipgpu_test_topk_route(int route) {
 
 int clipgpu_test_topk_narrow_rows(void) { return kNarrowRows; }
 
+int clipgpu_test_deep_cand(int n) {
+  return guarded([&]() {
+    if (n < 0 || n > kDeepCandMax)
+      throw ClipErr(CLIPGPU_ERR_INVALID, "n must be in 0.." + std::to_string(kDeepCandMax) + " (0 = default)");
+    g_deep_cand.store(n);
+  });
+}
+
 int clipgpu_test_topk_key(float score, uint32_t index, uint64_t* key) {
   return guarded([&]() {
     if (!key) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL key");

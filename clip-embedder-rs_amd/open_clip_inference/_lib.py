@@ -109,6 +109,10 @@ _PROTOS = [
                                            c_void_p, c_void_p, c_void_p, c_void_p]),
     ("clipgpu_index_search_coded_device", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_float,
                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("clipgpu_index_search_deep", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_void_p, c_void_p,
+                                          c_void_p, c_void_p]),
+    ("clipgpu_index_search_deep_device", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_void_p,
+                                                 c_void_p, c_void_p, c_void_p, c_void_p]),
     ("clipgpu_comm_unique_id", c_int, [c_void_p]),
     ("clipgpu_comm_init_rank", c_int, [c_void_p, c_void_p, c_int, c_int]),
     ("clipgpu_comm_info", c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
@@ -135,6 +139,7 @@ _PROTOS = [
     ("clipgpu_test_probe_parts", c_int, [c_int]),
     ("clipgpu_test_probe_chunk", c_int, [c_int]),
     ("clipgpu_test_codes_stage", c_int, [c_int]),
+    ("clipgpu_test_deep_cand", c_int, [c_int]),
     ("clipgpu_test_index_kmeans_sums", c_int, [c_void_p, c_int64, c_void_p, POINTER(c_int)]),
     ("clipgpu_test_index_kmeans_update", c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     ("clipgpu_test_gemm_lnf", c_int, [c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,

@@ -158,6 +158,14 @@ class Clip:
                                              allow=allow)
         return [[(int(i), float(s)) for i, s in zip(ri, rs) if i >= 0] for ri, rs in zip(idx, score)]
 
+    def search_deep(self, index, texts: Sequence[str], k: int, allow=None) -> List[List[Tuple[int, float]]]:
+        """``search`` for a long result list, 1 <= k <= 4096 (a page that scrolls, a candidate pool): what
+        ``search(index, texts, k, allow)`` would return if it took such a k, exactly
+        (``EmbeddingIndex.search_deep``)."""
+        scale, bias = self._scale_bias()
+        idx, score = index.search_deep(self.text.embed_texts(texts), k, float(scale), float(bias), allow=allow)
+        return [[(int(i), float(s)) for i, s in zip(ri, rs) if i >= 0] for ri, rs in zip(idx, score)]
+
     def search_above(self, index, texts: Sequence[str], min_logit: float, allow=None, max_results: int = 1 << 20
                      ) -> List[List[Tuple[int, float]]]:
         """``search`` by score instead of by count: per text EVERY row of ``index`` whose logit (the model's

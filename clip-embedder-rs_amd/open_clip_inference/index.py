@@ -13,6 +13,7 @@ import numpy as np
 from ._lib import check, lib
 
 TOPK_MAX = 128  # CLIPGPU_TOPK_MAX
+DEEP_K_MAX = 4096  # CLIPGPU_DEEP_K_MAX: the largest k of search_deep
 RANGE_MAX = 1 << 28  # most records of a range search or a self-join (include/clipgpu.h)
 MAX_CENTROIDS = 1 << 16  # most centroids of assign and kmeans (include/clipgpu.h)
 CODES_MAX_E = 1024  # the widest rows enable_codes takes (include/clipgpu.h)
@@ -54,7 +55,8 @@ class EmbeddingIndex:
     of the rounded rows returns (include/clipgpu.h has the bound on a logit's change).  ``remove``
     marks rows dead without moving the others, ``set_rows`` overwrites rows in place (and revives
     them), and ``search(..., allow=)`` searches a subset, exactly.  ``search_probs`` is the same search
-    with the softmax (over all searched rows) or sigmoid probabilities of the k results.  ``range_search``
+    with the softmax (over all searched rows) or sigmoid probabilities of the k results.  ``search_deep`` is
+    ``search`` for k up to 4096, as exact.  ``range_search``
     returns every row at or above a score threshold instead of the k best, and ``duplicates`` joins the
     gallery against itself at a threshold; neither builds the score matrix.  ``assign`` gives every row its
     nearest of C centroids and ``kmeans`` puts the rows into groups, reproducibly.  ``partition`` cuts the
@@ -207,6 +209,45 @@ class EmbeddingIndex:
                                                          float(logit_scale), float(logit_bias),
                                                          c_void_p(d_allow or None), c_void_p(d_idx), c_void_p(d_score),
                                                          c_void_p(stream or None)))
+
+    @staticmethod
+    def _deep_k(k) -> int:
+        """k, checked before any native call."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"k must be an integer, got {type(k).__name__}")
+        if not 1 <= int(k) <= DEEP_K_MAX:
+            raise ValueError(f"k must be in 1..{DEEP_K_MAX}, got {int(k)}")
+        return int(k)
+
+    def search_deep(self, queries, k: int, logit_scale: float = 1.0, logit_bias: float = 0.0, allow=None,
+                    return_passes: bool = False):
+        """``search`` for 1 <= k <= 4096: exactly the first k live (and allowed) rows per query in ``search``'s
+        order, with ``search``'s scores bit for bit and (-1, -inf) beyond the rows there are; for k <= 128 the
+        result is ``search``'s.  No score matrix and no k-deep list: a radix select finds each query's k-th key
+        in a few scans of the gallery, one more scan emits the rows at or above it and a sort orders them.
+        ``return_passes=True`` adds int32 [nq], the selection scans each query needed (1 .. 8; mass ties drive
+        it up).  The first call allocates the search's 36 MiB work area, kept until the index is closed."""
+        k = self._deep_k(k)
+        words = self._allow_words(allow)
+        q = self._rows(queries, "queries")
+        idx = np.empty((q.shape[0], k), np.int64)
+        score = np.empty((q.shape[0], k), np.float32)
+        passes = np.empty(q.shape[0], np.int32) if return_passes else None
+        check(lib().clipgpu_index_search_deep(self.handle, q.ctypes.data, q.shape[0], k, float(logit_scale),
+                                              float(logit_bias), None if words is None else words.ctypes.data,
+                                              idx.ctypes.data, score.ctypes.data,
+                                              None if passes is None else passes.ctypes.data))
+        return (idx, score, passes) if return_passes else (idx, score)
+
+    def search_deep_device(self, d_queries: int, nq: int, k: int, d_idx: int, d_score: int, logit_scale: float = 1.0,
+                           logit_bias: float = 0.0, stream: int = 0, d_allow: int = 0, d_passes: int = 0) -> None:
+        """``search_deep`` on device pointers (as ``search_device``; ``d_passes`` int32 [nq] out or 0 = not
+        wanted), ordered on ``stream``; enqueues a fixed sequence of launches and returns without
+        synchronising."""
+        check(lib().clipgpu_index_search_deep_device(self.handle, c_void_p(d_queries), int(nq), self._deep_k(k),
+                                                     float(logit_scale), float(logit_bias), c_void_p(d_allow or None),
+                                                     c_void_p(d_idx), c_void_p(d_score), c_void_p(d_passes or None),
+                                                     c_void_p(stream or None)))
 
     @staticmethod
     def _range_args(threshold, limit, what: str) -> Tuple[float, int]:

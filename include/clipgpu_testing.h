@@ -308,6 +308,11 @@ int clipgpu_test_probe_chunk(int rows);
  * the results are not written), 2 = the re-rank only, on the candidates the last coarse stage left in the handle
  * (meaningful for the same queries, at most 256 of them). */
 int clipgpu_test_codes_stage(int stage);
+/* The candidate capacity per query of a deep search (clipgpu_index_search_deep[_device]), process-wide and
+ * atomic, for every deep search started afterwards: 0 = the default (8192), else 1 .. 8192.  The effective
+ * capacity is max(k, n): with n = 1 the select resolves all the way to the k-th key, so a small gallery walks
+ * every digit.  The result never depends on it; the pass counts do. */
+int clipgpu_test_deep_cand(int n);
 
 #ifdef __cplusplus
 }

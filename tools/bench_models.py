@@ -615,6 +615,83 @@ def codes_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 16, 256), refines
         assert verdict[0] < verdict[1], f"coded max {verdict[0]} ms is not below plain min {verdict[1]} ms"
 
 
+def topk_deep_leg(N=1 << 20, E=512, runs=5, warmup=2, Qs=(1, 16, 256), ks=(129, 1000, 4096), centres=1024, sigma=0.05):
+    """The deep search (search_deep_device, 128 < k <= 4096) on the ivf leg's clustered f32 gallery.  Per (Q, k),
+    legs alternating in one process (rotating order, device-event timings after `warmup` rounds): the deep search;
+    the path a caller had before it, clipgpu_similarity_device logits into a [Q][N] tensor and torch.topk(k);
+    search_device at k = 128; and range_search_device at a threshold that about k rows per query pass (the median
+    k-th score), which is the cost of one scan of the loop the deep search runs (passes + 1) times.  The deep
+    result is checked against the matrix path (score bits; indices once its ties are in index order).  Beside the
+    times: the histogram passes per query (min, median, max)."""
+    import ctypes
+    from open_clip_inference import EmbeddingIndex
+    torch.manual_seed(0)
+    L = _lib.lib()
+    s = torch.cuda.current_stream().cuda_stream
+    cen0 = torch.nn.functional.normalize(torch.randn(centres, E, device="cuda"), dim=1)
+
+    def draw(n):
+        return torch.nn.functional.normalize(cen0[torch.randint(0, centres, (n,), device="cuda")] +
+                                             sigma * torch.randn(n, E, device="cuda"), dim=1).contiguous()
+
+    g = draw(N)
+    qs = {Q: draw(Q) for Q in Qs}
+    with EmbeddingIndex(E, N) as ix:
+        ix.add_device(g.data_ptr(), N, s)
+        for Q in Qs:
+            q = qs[Q]
+            mat = torch.empty(Q, N, device="cuda")
+            i128, s128 = torch.empty((Q, 128), dtype=torch.int64, device="cuda"), torch.empty((Q, 128), device="cuda")
+            for k in ks:
+                idx, sc = torch.empty((Q, k), dtype=torch.int64, device="cuda"), torch.empty((Q, k), device="cuda")
+                passes = torch.zeros(Q, dtype=torch.int32, device="cuda")
+                base = {}
+
+                def deep():
+                    ix.search_deep_device(q.data_ptr(), Q, k, idx.data_ptr(), sc.data_ptr(), 100.0, 0.0, s,
+                                          d_passes=passes.data_ptr())
+
+                def matrix():
+                    _lib.check(L.clipgpu_similarity_device(ctypes.c_void_p(q.data_ptr()), Q, ctypes.c_void_p(g.data_ptr()),
+                                                           N, E, 100.0, 0.0, 2, 1, ctypes.c_void_p(mat.data_ptr()),
+                                                           ctypes.c_void_p(s)))
+                    base["score"], base["idx"] = torch.topk(mat, k, dim=1)
+
+                deep()
+                thr = float(sc[:, k - 1].median())
+                cap = 2 * Q * k + 1024
+                rec = (torch.empty(cap, dtype=torch.int32, device="cuda"), torch.empty(cap, dtype=torch.int32, device="cuda"),
+                       torch.empty(cap, device="cuda"))
+                tot = torch.zeros(1, dtype=torch.int64, device="cuda")
+                legs = [("deep", deep), ("matrix_topk", matrix),
+                        ("search128", lambda: ix.search_device(q.data_ptr(), Q, 128, i128.data_ptr(), s128.data_ptr(),
+                                                               100.0, 0.0, s)),
+                        ("range", lambda: ix.range_search_device(q.data_ptr(), Q, thr, cap, rec[0].data_ptr(),
+                                                                 rec[1].data_ptr(), rec[2].data_ptr(), tot.data_ptr(),
+                                                                 100.0, 0.0, s))]
+                ms = {name: [] for name, _ in legs}
+                for rnd in range(warmup + runs):
+                    r = rnd % len(legs)
+                    for name, fn in legs[r:] + legs[:r]:  # every leg follows every other equally often
+                        t = _event_ms(fn)
+                        if rnd >= warmup:
+                            ms[name].append(t)
+                b_idx, b_score = base["idx"].cpu().numpy(), base["score"].cpu().numpy()
+                order = np.lexsort((b_idx, -b_score.astype(np.float64)), axis=1)
+                b_idx, b_score = np.take_along_axis(b_idx, order, 1), np.take_along_axis(b_score, order, 1)
+                assert np.array_equal(sc.cpu().numpy().view(np.uint32), b_score.view(np.uint32))
+                assert np.array_equal(idx.cpu().numpy(), b_idx)
+                p = passes.cpu().numpy()
+                out = {"measure": "topk_deep", "Q": Q, "k": k, "N": N, "E": E, "runs": runs, "same_as_matrix_topk": True,
+                       "passes_min_median_max": [int(p.min()), float(np.median(p)), int(p.max())],
+                       "range_hits": int(tot)}
+                for name, v in ms.items():
+                    out[name] = _stats(v, N * E * 4)
+                out["deep_over_matrix_topk"] = round(out["deep"]["ms_median"] / out["matrix_topk"]["ms_median"], 3)
+                out["deep_over_range"] = round(out["deep"]["ms_median"] / out["range"]["ms_median"], 2)
+                print(json.dumps(out), flush=True)
+
+
 def topk_routes_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 2, 4, 8, 12, 16)):
     """The measurement kNarrowRows (csrc/kernels/kernels.hpp) is set by: for every query count the
     few-query kernel can take, that kernel (route 2) against the wide one (route 1) on an f32 gallery,
@@ -843,6 +920,8 @@ if __name__ == "__main__":
         topk_probs_leg()
     if "topkrange" in which:  # the range search against search k = 10, dense emission, and the self-join
         topk_range_leg()
+    if "topkdeep" in which:  # the deep search (k up to 4096) against similarity + torch.topk, search k = 128, one range scan
+        topk_deep_leg()
     if "kmeans" in which:  # one k-means iteration: assign against the range search, the integer-sum update
         kmeans_leg()
     if "ivf" in which:  # the probed search against the plain search on a clustered gallery
