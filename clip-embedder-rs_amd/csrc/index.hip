@@ -51,6 +51,11 @@
 // chunks, route and span cut as a search; per chunk launch_deep enqueues its fixed sequence of launches into a
 // work area of the handle's (the chunk's histograms, state and candidate records, and the host form's staged
 // results), allocated at the first deep search and kept until the handle is destroyed.
+//
+// Compound queries (clipgpu_index_search_compound[_device]; kernels/compound.hip): a query is a group of 1 .. 16
+// terms, scored by the smallest or the largest of its term logits.  The same chunks of 256 queries; per chunk a
+// gather pads the groups to the chunk's slot width into a buffer of the handle's (lazy, as the deep search's),
+// the compound phase 1 fills the search workspace and the search's merge writes the result.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -137,6 +142,8 @@ struct clipgpu_index {
   char* cd_work = nullptr;       // a coded search in flight: the regions carve_codes places
   int64_t cd_Ep = 0;
   char* dp_work = nullptr;       // the deep search: what deep_buffers carves; lazy, kept until the handle is destroyed
+  char* cp_work = nullptr;       // compound queries: what compound_buffers places; lazy, kept likewise
+  int64_t cp_work_n = 0;
   hipStream_t stream = nullptr;  // the host-buffer forms' stream
   hipEvent_t done = nullptr;     // recorded after every device-side operation
 };
@@ -780,9 +787,132 @@ int deep_host(clipgpu_index* ix, const DeepReq& r, const DeepOut& o) {
   });
 }
 
+// ---- compound queries (kernels/compound.hip) --------------------------------------------------------------
+// One call.  Host form: terms [T][E] and lims int64 [nq + 1] on the host, checked here.  Device form: d_terms and
+// d_lims (int32) on the device, max_terms the caller's bound on a group's size (the device clamps to it).
+struct CompoundReq { const float* terms; int64_t T, nq, k; int op; float scale, bias; const uint32_t* allow; };
+
+// The regions of cp_work: a chunk's offsets, its staged terms (host form) and its padded tile rows.
+struct CompoundWork { int32_t* lims; float* terms; float* tiles; };
+constexpr size_t kCompoundRows = (size_t)kQueryChunk * kCompoundTermsMax;  // most terms, and tile rows, of a chunk
+// Allocated at the first compound search (grow: the owner of the handle's lazy buffers) and kept until the handle
+// is destroyed; a failed allocation is CLIPGPU_ERR_DEVICE and leaves the handle without the area, usable.
+// Callers hold the mutex.
+CompoundWork compound_buffers(clipgpu_index* ix) {
+  const size_t rows_bytes = align256(kCompoundRows * ix->E * 4);
+  grow(ix->cp_work, ix->cp_work_n, 1, 2048 + 2 * rows_bytes);
+  CompoundWork w;
+  w.lims = (int32_t*)ix->cp_work;  // kQueryChunk + 1 offsets: 1028 bytes
+  w.terms = (float*)(ix->cp_work + 2048);
+  w.tiles = (float*)(ix->cp_work + 2048 + rows_bytes);
+  return w;
+}
+
+// The refusals that need no lock, in the order the header lists them; then as enter_search.
+std::unique_lock<std::mutex> enter_compound(clipgpu_index* ix, const CompoundReq& r, bool null_arg) {
+  if (!ix || null_arg) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+  if (r.nq <= 0 || r.T <= 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
+  if (r.k < 1 || r.k > CLIPGPU_TOPK_MAX)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "k must be in 1.." + std::to_string(CLIPGPU_TOPK_MAX) + ", got " +
+                                           std::to_string(r.k));
+  if (r.op != CLIPGPU_COMPOUND_MIN && r.op != CLIPGPU_COMPOUND_MAX)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "op must be CLIPGPU_COMPOUND_MIN (0) or CLIPGPU_COMPOUND_MAX (1), got " +
+                                           std::to_string(r.op));
+  std::unique_lock<std::mutex> lk(ix->mu);
+  if (ix->size == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");  // an empty gallery
+  HIP_CHECK(hipSetDevice(ix->device));
+  return lk;
+}
+
+std::string terms_range() { return "1.." + std::to_string(CLIPGPU_COMPOUND_TERMS_MAX) + " terms (CLIPGPU_COMPOUND_TERMS_MAX)"; }
+
+// One chunk of `rows` compound queries on `s`: d_lims (device int32 [rows + 1]) into d_terms [T][E], slot width
+// G.  The gather pads the tile rows into cp_work, the phase 1 fills the search workspace, the merge writes the
+// result.  Stream order keeps the chunks of a call, which share both, apart.
+void compound_chunk(clipgpu_index* ix, const CompoundReq& r, const float* d_terms, const int32_t* d_lims, int rows,
+                    int G, const uint32_t* mask, float* tiles, int64_t* d_idx, float* d_score, hipStream_t s) {
+  HIP_CHECK(launch_compound_gather(d_terms, (long)r.T, d_lims, rows, G, (int)ix->E, tiles, s));
+  const TopkPlan p = compound_plan(ix->size, rows, G, ix->ws_blocks);
+  HIP_CHECK(launch_compound({tiles, rows, G, r.op, ix->gallery, ix->dtype, (int)ix->size, (int)ix->E, r.scale, r.bias,
+                             (int)r.k, p, ix->d_ws, mask, s}));
+  HIP_CHECK(launch_topk_merge(ix->d_ws, rows, p.n_spans, (int)r.k, d_idx, d_score, s));
+}
+
+int compound_device(clipgpu_index* ix, const CompoundReq& r, const int32_t* d_lims, int64_t max_terms, int64_t* d_idx,
+                    float* d_score, hipStream_t s) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_compound(ix, r, !r.terms || !d_lims || !d_idx || !d_score);
+    if (max_terms < 1 || max_terms > CLIPGPU_COMPOUND_TERMS_MAX)
+      throw ClipErr(CLIPGPU_ERR_INVALID, "max_terms: a group has " + terms_range() + ", got " + std::to_string(max_terms));
+    if (r.T > INT32_MAX) throw ClipErr(CLIPGPU_ERR_INVALID, "too many terms (d_lims holds int32)");
+    if ((uintptr_t)r.terms & 15) throw ClipErr(CLIPGPU_ERR_INVALID, "d_terms must be 16-byte aligned");
+    const CompoundWork w = compound_buffers(ix);
+    order_after_last(ix, s);
+    const uint32_t* mask = build_mask(ix, r.allow, s);
+    const int G = compound_width((int)max_terms);
+    for (int64_t q0 = 0; q0 < r.nq; q0 += kQueryChunk)
+      compound_chunk(ix, r, r.terms, d_lims + q0, (int)std::min(kQueryChunk, r.nq - q0), G, mask, w.tiles,
+                     d_idx + q0 * r.k, d_score + q0 * r.k, s);
+    mark_last(ix, s);
+  });
+}
+
+int compound_host(clipgpu_index* ix, const CompoundReq& r, const int64_t* lims, int64_t* out_idx, float* out_score) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_compound(ix, r, !r.terms || !lims || !out_idx || !out_score);
+    if (lims[0] != 0) throw ClipErr(CLIPGPU_ERR_INVALID, "lims must start at 0, got " + std::to_string(lims[0]));
+    for (int64_t q = 0; q < r.nq; ++q) {
+      const int64_t n = lims[q + 1] - lims[q];
+      if (n < 0) throw ClipErr(CLIPGPU_ERR_INVALID, "lims must be ascending (at query " + std::to_string(q) + ")");
+      if (n < 1 || n > CLIPGPU_COMPOUND_TERMS_MAX)
+        throw ClipErr(CLIPGPU_ERR_INVALID, "a query has " + terms_range() + ", query " + std::to_string(q) + " has " +
+                                               std::to_string(n));
+    }
+    if (lims[r.nq] != r.T)
+      throw ClipErr(CLIPGPU_ERR_INVALID, "lims must end at the number of terms, " + std::to_string(r.T) + ", got " +
+                                             std::to_string(lims[r.nq]));
+    HIP_CHECK(hipEventSynchronize(ix->done));  // the staging buffers and the filter area are free
+    const CompoundWork w = compound_buffers(ix);
+    if (r.allow) HIP_CHECK(copy_h2d(ix->d_eff, r.allow, (size_t)live_words(ix->size) * 4));
+    const uint32_t* mask = build_mask(ix, r.allow ? ix->d_eff : nullptr, ix->stream);
+    std::vector<int32_t> rel((size_t)kQueryChunk + 1);
+    for (int64_t q0 = 0; q0 < r.nq; q0 += kQueryChunk) {
+      // the chunk's terms and its offsets from the first of them; its slot width from its own largest group
+      const int rows = (int)std::min(kQueryChunk, r.nq - q0);
+      int largest = 1;
+      for (int q = 0; q <= rows; ++q) rel[q] = (int32_t)(lims[q0 + q] - lims[q0]);
+      for (int q = 0; q < rows; ++q) largest = std::max(largest, rel[q + 1] - rel[q]);
+      CompoundReq c = r;
+      c.T = rel[rows];
+      HIP_CHECK(copy_h2d(w.lims, rel.data(), (size_t)(rows + 1) * 4));
+      HIP_CHECK(copy_h2d(w.terms, r.terms + lims[q0] * ix->E, (size_t)c.T * ix->E * 4));
+      compound_chunk(ix, c, w.terms, w.lims, rows, compound_width(largest), mask, w.tiles, ix->st_idx, ix->st_score,
+                     ix->stream);
+      mark_last(ix, ix->stream);
+      HIP_CHECK(hipStreamSynchronize(ix->stream));
+      HIP_CHECK(copy_d2h(out_idx + q0 * r.k, ix->st_idx, (size_t)rows * r.k * 8));
+      HIP_CHECK(copy_d2h(out_score + q0 * r.k, ix->st_score, (size_t)rows * r.k * 4));
+    }
+  });
+}
+
 }  // namespace
 
 extern "C" {
+
+int clipgpu_index_search_compound(clipgpu_index* ix, const float* terms, int64_t n_terms, const int64_t* lims,
+                                  int64_t nq, int64_t k, int op, float logit_scale, float logit_bias,
+                                  const uint32_t* allow, int64_t* out_idx, float* out_score) {
+  return compound_host(ix, {terms, n_terms, nq, k, op, logit_scale, logit_bias, allow}, lims, out_idx, out_score);
+}
+
+int clipgpu_index_search_compound_device(clipgpu_index* ix, const float* d_terms, int64_t n_terms, const int32_t* d_lims,
+                                         int64_t nq, int64_t max_terms, int64_t k, int op, float logit_scale,
+                                         float logit_bias, const uint32_t* d_allow, int64_t* d_idx, float* d_score,
+                                         void* stream) {
+  return compound_device(ix, {d_terms, n_terms, nq, k, op, logit_scale, logit_bias, d_allow}, d_lims, max_terms, d_idx,
+                         d_score, (hipStream_t)stream);
+}
 
 int clipgpu_index_search_deep(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, float logit_scale,
                               float logit_bias, const uint32_t* allow, int64_t* out_idx, float* out_score,
@@ -1110,6 +1240,7 @@ void clipgpu_index_destroy(clipgpu_index* ix) {
   if (ix->cd_scale) (void)hipFree(ix->cd_scale);
   if (ix->cd_work) (void)hipFree(ix->cd_work);
   if (ix->dp_work) (void)hipFree(ix->dp_work);
+  if (ix->cp_work) (void)hipFree(ix->cp_work);
   if (ix->work) (void)hipFree(ix->work);
   if (ix->gallery) (void)hipFree(ix->gallery);
   delete ix;

@@ -253,6 +253,36 @@ hipError_t launch_topk_mask(const uint32_t* live, const uint32_t* allow, uint32_
 hipError_t launch_topk_merge(const void* ws, int nq, int n_spans, int k, int64_t* out_idx, float* out_score,
                              hipStream_t s);
 
+// Compound-query phase 1 (kernels/compound.hip): a query is a group of 1 .. kCompoundTermsMax term rows and a
+// gallery row's score is the term logit (launch_topk's, bit for bit) whose topk_mono is smallest (COMPOUND_MIN)
+// or largest (COMPOUND_MAX), as the bits of the inverse of topk_mono: a zero is +0.0, a NaN 0x7fc00000.  Per
+// (query, span) the k largest topk_key(those bits, row) over the rows mask allows go to ws in the layout
+// launch_topk_merge reads.  G, the slot width: compound_width(the largest group of the launch).  tiles: the
+// padded rows launch_compound_gather writes, f32 [ceil(nq G / 16) * 16][E], 16-byte aligned: query q's terms in
+// rows [q G, (q + 1) G), a short group filled up with its first term.  lims: device int32 [nq + 1], offsets of
+// the groups in terms [T][E]; a group is clamped to 1 .. G terms and every term into [0, T).  The plan is
+// compound_plan(N, nq, G, ...): the search's span cut (g_topk_span_cols too) for one-wave blocks, such that the
+// workspace of max_blocks wide blocks holds nq * n_spans rows.
+constexpr int kCompoundTermsMax = 16;
+enum CompoundOp { COMPOUND_MIN = 0, COMPOUND_MAX = 1 };
+int compound_width(int largest);
+TopkPlan compound_plan(long N, int nq, int G, int max_blocks);
+hipError_t launch_compound_gather(const float* terms, long T, const int32_t* lims, int nq, int G, int E, float* tiles,
+                                  hipStream_t s);
+struct CompoundArgs {
+  const float* tiles;
+  int nq, G, op;
+  const void* g;  // [N][E] of dtype (TopkGal)
+  int dtype, N, E;
+  float scale, bias;
+  int k;
+  TopkPlan plan;
+  void* ws;
+  const uint32_t* mask;
+  hipStream_t stream;
+};
+hipError_t launch_compound(const CompoundArgs& a);
+
 // Inverted lists (kernels/lists.hip): the CSR of the rows by label.  label: int32 [N], -1 = not in any list,
 // else below C (1 <= C <= kClusterMaxCentroids).  offsets int32 [C + 1]: offsets[c] = the rows with a label
 // below c; ids int32 [offsets[C]]: the rows of list c at [offsets[c], offsets[c + 1]), ascending -- a pure

@@ -7,9 +7,9 @@ runs in ``lib/libclipgpu.so`` (hand-written gfx950 HIP kernels + C++ host runtim
 from .clip import Clip
 from .config import ModelConfig, OpenClipConfig
 from .error import ClipError, ResultOverflow
-from .index import DEEP_K_MAX, EmbeddingIndex, KMeansResult, pack_allow
+from .index import COMPOUND_OPS, COMPOUND_TERMS_MAX, DEEP_K_MAX, EmbeddingIndex, KMeansResult, pack_allow
 from .text import TextEmbedder
 from .vision import VisionEmbedder
 
 __all__ = ["Clip", "ClipError", "ResultOverflow", "EmbeddingIndex", "KMeansResult", "pack_allow", "DEEP_K_MAX",
-           "TextEmbedder", "VisionEmbedder", "ModelConfig", "OpenClipConfig"]
+           "COMPOUND_TERMS_MAX", "COMPOUND_OPS", "TextEmbedder", "VisionEmbedder", "ModelConfig", "OpenClipConfig"]

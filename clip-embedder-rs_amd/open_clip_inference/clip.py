@@ -166,6 +166,30 @@ class Clip:
         idx, score = index.search_deep(self.text.embed_texts(texts), k, float(scale), float(bias), allow=allow)
         return [[(int(i), float(s)) for i, s in zip(ri, rs) if i >= 0] for ri, rs in zip(idx, score)]
 
+    def _search_groups(self, index, groups, k: int, op: str, allow) -> List[List[Tuple[int, float]]]:
+        groups = [list(g) for g in groups]
+        lims = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int64)
+        scale, bias = self._scale_bias()
+        flat = [t for g in groups for t in g]
+        if not flat:
+            raise ValueError("Empty batch: no texts")
+        idx, score = index.search_compound(self.text.embed_texts(flat), lims, k, op, float(scale), float(bias),
+                                           allow=allow)
+        return [[(int(i), float(s)) for i, s in zip(ri, rs) if i >= 0] for ri, rs in zip(idx, score)]
+
+    def search_all(self, index, groups: Sequence[Sequence[str]], k: int, allow=None) -> List[List[Tuple[int, float]]]:
+        """``search`` for conjunctions: per group of 1 to 16 texts (``["a dog", "a beach"]``) the k best rows by
+        the SMALLEST of the group's logits -- rows that match every text -- as (gallery index, that logit), best
+        first.  All texts are embedded in one batch and the gallery is scanned once
+        (``EmbeddingIndex.search_compound`` with "min")."""
+        return self._search_groups(index, groups, k, "min", allow)
+
+    def search_any(self, index, groups: Sequence[Sequence[str]], k: int, allow=None) -> List[List[Tuple[int, float]]]:
+        """``search`` for prompt ensembles and synonyms: per group of 1 to 16 texts the k best rows by the
+        LARGEST of the group's logits, as (gallery index, that logit), best first
+        (``EmbeddingIndex.search_compound`` with "max")."""
+        return self._search_groups(index, groups, k, "max", allow)
+
     def search_above(self, index, texts: Sequence[str], min_logit: float, allow=None, max_results: int = 1 << 20
                      ) -> List[List[Tuple[int, float]]]:
         """``search`` by score instead of by count: per text EVERY row of ``index`` whose logit (the model's

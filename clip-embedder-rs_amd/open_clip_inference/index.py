@@ -14,6 +14,8 @@ from ._lib import check, lib
 
 TOPK_MAX = 128  # CLIPGPU_TOPK_MAX
 DEEP_K_MAX = 4096  # CLIPGPU_DEEP_K_MAX: the largest k of search_deep
+COMPOUND_TERMS_MAX = 16  # CLIPGPU_COMPOUND_TERMS_MAX: the most terms of one compound query
+COMPOUND_OPS = {"min": 0, "max": 1}  # CLIPGPU_COMPOUND_MIN (all-of), CLIPGPU_COMPOUND_MAX (any-of)
 RANGE_MAX = 1 << 28  # most records of a range search or a self-join (include/clipgpu.h)
 MAX_CENTROIDS = 1 << 16  # most centroids of assign and kmeans (include/clipgpu.h)
 CODES_MAX_E = 1024  # the widest rows enable_codes takes (include/clipgpu.h)
@@ -56,7 +58,8 @@ class EmbeddingIndex:
     marks rows dead without moving the others, ``set_rows`` overwrites rows in place (and revives
     them), and ``search(..., allow=)`` searches a subset, exactly.  ``search_probs`` is the same search
     with the softmax (over all searched rows) or sigmoid probabilities of the k results.  ``search_deep`` is
-    ``search`` for k up to 4096, as exact.  ``range_search``
+    ``search`` for k up to 4096, as exact.  ``search_compound`` takes queries made of up to 16 terms and scores a
+    row by the smallest (all-of) or largest (any-of) of its term logits, in one scan.  ``range_search``
     returns every row at or above a score threshold instead of the k best, and ``duplicates`` joins the
     gallery against itself at a threshold; neither builds the score matrix.  ``assign`` gives every row its
     nearest of C centroids and ``kmeans`` puts the rows into groups, reproducibly.  ``partition`` cuts the
@@ -248,6 +251,67 @@ class EmbeddingIndex:
                                                      float(logit_scale), float(logit_bias), c_void_p(d_allow or None),
                                                      c_void_p(d_idx), c_void_p(d_score), c_void_p(d_passes or None),
                                                      c_void_p(stream or None)))
+
+    # ---- compound queries ------------------------------------------------------------------------------
+    @staticmethod
+    def _compound_args(k, op) -> Tuple[int, int]:
+        """(k, the op's enum value), checked before any native call."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"k must be an integer, got {type(k).__name__}")
+        if not 1 <= int(k) <= TOPK_MAX:
+            raise ValueError(f"k must be in 1..{TOPK_MAX}, got {int(k)}")
+        if op not in COMPOUND_OPS:
+            raise ValueError(f"op must be one of {sorted(COMPOUND_OPS)}, got {op!r}")
+        return int(k), COMPOUND_OPS[op]
+
+    def search_compound(self, terms, lims, k: int, op: str, logit_scale: float = 1.0, logit_bias: float = 0.0,
+                        allow=None) -> Tuple[np.ndarray, np.ndarray]:
+        """``search`` for queries made of several terms.  ``terms`` f32 [T, E]; ``lims`` integers [Q + 1] with
+        ``lims[0] == 0`` and ``lims[Q] == T``: compound query q owns ``terms[lims[q]:lims[q + 1]]``, 1 to 16 of
+        them, and one call may mix sizes.  A row's score is the smallest (``op="min"``: all-of, "a dog" AND "a
+        beach") or the largest (``op="max"``: any-of, a prompt ensemble) of its term logits, each with
+        ``similarity``'s bits; it comes back as +0.0 if it is a zero and as the canonical NaN if it is one.  Under
+        "min" a NaN term makes the score NaN (ranked last, still an entry); under "max" a NaN term is ignored
+        unless all are.  Returns (indices int64 [Q, k], scores f32 [Q, k]): the k best live allowed rows per
+        query, best first, equal scores by ascending row, (-1, -inf) beyond the rows there are -- exact and
+        bit-reproducible, without the [T, N] matrix.  A one-term query is ``search``.  1 <= k <= 128."""
+        k, opv = self._compound_args(k, op)
+        words = self._allow_words(allow)
+        t = self._rows(terms, "terms")
+        l = np.asarray(lims)
+        if l.ndim != 1 or l.size < 2 or not np.issubdtype(l.dtype, np.integer):
+            raise ValueError("lims must be a 1-d array of at least two integers: [0, ..., T]")
+        l = np.ascontiguousarray(l, dtype=np.int64)
+        n = np.diff(l)
+        if l[0] != 0 or l[-1] != t.shape[0] or (n < 0).any():
+            raise ValueError(f"lims must ascend from 0 to the number of terms, {t.shape[0]}")
+        if (n < 1).any() or (n > COMPOUND_TERMS_MAX).any():
+            raise ValueError(f"a compound query has 1..{COMPOUND_TERMS_MAX} terms, got groups of {int(n.min())} to "
+                             f"{int(n.max())}")
+        Q = l.size - 1
+        idx = np.empty((Q, k), np.int64)
+        score = np.empty((Q, k), np.float32)
+        check(lib().clipgpu_index_search_compound(self.handle, t.ctypes.data, t.shape[0], l.ctypes.data, Q, k, opv,
+                                                  float(logit_scale), float(logit_bias),
+                                                  None if words is None else words.ctypes.data, idx.ctypes.data,
+                                                  score.ctypes.data))
+        return idx, score
+
+    def search_compound_device(self, d_terms: int, n_terms: int, d_lims: int, nq: int, k: int, op: str, d_idx: int,
+                               d_score: int, logit_scale: float = 1.0, logit_bias: float = 0.0, stream: int = 0,
+                               d_allow: int = 0, max_terms: int = COMPOUND_TERMS_MAX) -> None:
+        """``search_compound`` on device pointers (terms f32 [n_terms, E], 16-byte aligned, and lims int32
+        [nq + 1] in; int64 [nq, k] and f32 [nq, k] out), ordered on ``stream``; returns without synchronising.
+        The offsets cannot be checked without reading them back: ``max_terms`` (1..16) is the caller's bound on
+        the size of a group -- 16 is always valid, a tighter bound is faster -- and the device clamps every
+        group to 1..max_terms terms inside ``d_terms``."""
+        k, opv = self._compound_args(k, op)
+        if not 1 <= int(max_terms) <= COMPOUND_TERMS_MAX:
+            raise ValueError(f"max_terms must be in 1..{COMPOUND_TERMS_MAX}, got {int(max_terms)}")
+        check(lib().clipgpu_index_search_compound_device(self.handle, c_void_p(d_terms), int(n_terms), c_void_p(d_lims),
+                                                         int(nq), int(max_terms), k, opv, float(logit_scale),
+                                                         float(logit_bias), c_void_p(d_allow or None), c_void_p(d_idx),
+                                                         c_void_p(d_score), c_void_p(stream or None)))
 
     @staticmethod
     def _range_args(threshold, limit, what: str) -> Tuple[float, int]:

@@ -595,6 +595,51 @@ int clipgpu_index_search_deep_device(clipgpu_index* ix, const float* d_queries, 
                                      float logit_scale, float logit_bias, const uint32_t* d_allow, int64_t* d_idx,
                                      float* d_score, int32_t* d_passes, void* stream);
 
+/* ---- compound queries: all-of / any-of groups of terms in one scan ------------------------------------------
+ * Every other search scores a row against ONE query vector.  Here a query is a group of 1 ..
+ * CLIPGPU_COMPOUND_TERMS_MAX term vectors: "a dog" AND "a beach" is the rows that score well against both
+ * (CLIPGPU_COMPOUND_MIN, the smallest of the term logits), a prompt ensemble or a list of synonyms is the best of
+ * several (CLIPGPU_COMPOUND_MAX, the largest).  min and max are not linear, so a group cannot be folded into one
+ * vector, and the k best of each term need not contain the k best of the minimum; the [terms][size] matrix is
+ * never built: the terms of a group are rows of the kernel's MFMA tile and are reduced there
+ * (kernels/compound.hip; DESIGN.md, embedding index, compound queries).
+ * terms f32 [n_terms][E]; lims [nq + 1] with lims[0] == 0 and lims[nq] == n_terms: query q owns
+ * terms[lims[q] .. lims[q + 1]), 1 .. 16 of them; one call may mix group sizes.
+ * Score: l_t(j) = fmaf(dot(term_t, row j), logit_scale, logit_bias), clipgpu_similarity's bits; the fused score
+ * of row j is the term logit that is smallest (MIN) or largest (MAX) in the search's order of scores (+0.0 ==
+ * -0.0, a NaN below -inf), returned in canonical bits: a zero as +0.0, a NaN as 0x7fc00000.  So under MIN a NaN
+ * term makes the fused score NaN (the row ranks last but is an entry, as in the search); under MAX a NaN term is
+ * ignored unless every term is NaN.  Result: per query the k best live allowed rows by (fused score descending,
+ * row ascending), out_idx int64 [nq][k] and out_score f32 [nq][k], (-1, -inf) beyond the rows there are: exact,
+ * independent of any order of evaluation, bit-reproducible.  A one-term query returns clipgpu_index_search's ids
+ * and order, and its scores up to the canonical zero / NaN.  1 <= k <= CLIPGPU_TOPK_MAX; `allow`, removed rows and
+ * the three storage types as in the filtered search.  Not offered: negative terms (an allow bitmap built from a
+ * range search expresses them), per-term weights, probabilities, k above 128, probed and coded forms.
+ * The _device form: d_terms (16-byte aligned), d_lims (int32), d_idx, d_score on the device, ordered on `stream`,
+ * nothing read back, no synchronisation -- so it cannot check d_lims: max_terms (1 .. 16) is the caller's bound
+ * on the size of a group, from which the tile layout follows (16 is always valid, a tighter bound is faster), and
+ * the device clamps every group to 1 .. max_terms terms inside d_terms: offsets that break the promise give the
+ * results of the clamped groups, never a read outside d_terms.
+ * Work area: a chunk of 256 queries' offsets, staged terms and padded tiles (2 x 4096 rows of E f32) are one
+ * device buffer that the handle allocates at the first compound search and keeps until it is destroyed (a failed
+ * allocation is CLIPGPU_ERR_DEVICE and leaves the index usable).  Mutex, event ordering, chunking and host
+ * staging are those of the other searches.
+ * Refused with CLIPGPU_ERR_INVALID before any device call: a NULL argument; nq <= 0, n_terms <= 0 or an empty
+ * index ("Empty batch"); k outside 1 .. CLIPGPU_TOPK_MAX; an op that is neither constant; (host form) lims that
+ * does not start at 0, is not ascending or does not end at n_terms, and a query with 0 or more than
+ * CLIPGPU_COMPOUND_TERMS_MAX terms; (device form) max_terms outside 1 .. CLIPGPU_COMPOUND_TERMS_MAX.  Each message
+ * names the limit. */
+#define CLIPGPU_COMPOUND_TERMS_MAX 16
+#define CLIPGPU_COMPOUND_MIN 0
+#define CLIPGPU_COMPOUND_MAX 1
+int clipgpu_index_search_compound(clipgpu_index* ix, const float* terms, int64_t n_terms, const int64_t* lims,
+                                  int64_t nq, int64_t k, int op, float logit_scale, float logit_bias,
+                                  const uint32_t* allow, int64_t* out_idx, float* out_score);
+int clipgpu_index_search_compound_device(clipgpu_index* ix, const float* d_terms, int64_t n_terms,
+                                         const int32_t* d_lims, int64_t nq, int64_t max_terms, int64_t k, int op,
+                                         float logit_scale, float logit_bias, const uint32_t* d_allow,
+                                         int64_t* d_idx, float* d_score, void* stream);
+
 /* ---- data-parallel sharding + the RCCL all-gather (north_star: "batches shard
  * data-parallel across the 8 GPUs of one node with an RCCL all-gather over xGMI only for the final
  * embedding matrix").  The reference has no multi-device path: embed_images / embed_texts

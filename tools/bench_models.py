@@ -692,6 +692,70 @@ def topk_deep_leg(N=1 << 20, E=512, runs=5, warmup=2, Qs=(1, 16, 256), ks=(129, 
                 print(json.dumps(out), flush=True)
 
 
+def topk_compound_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 16, 256), sizes=(2, 4, 16)):
+    """Compound queries (search_compound_device: Q groups of `size` terms, min) over an f32 gallery.  Per (Q, size),
+    legs alternating in one process (rotating order, device-event timings after `warmup` rounds): the compound
+    search; the only path a caller had before it -- clipgpu_similarity_device logits of all T = Q * size terms into
+    a [T][N] tensor (its bytes are reported), torch.amin over each group, torch.topk; and, for scale,
+    search_device with the T terms as plain queries (the same scan work, the answer to another question).  The
+    compound result is checked against the matrix path (score bits; indices once its ties are in index order).
+    After each cell's rounds a 2 ms one-wave probe reads the shader clock as the load ends."""
+    import ctypes
+    from open_clip_inference import EmbeddingIndex
+    torch.manual_seed(0)
+    L = _lib.lib()
+    s = torch.cuda.current_stream().cuda_stream
+    probe = torch.zeros(2, dtype=torch.int64, device="cuda")
+    g = torch.nn.functional.normalize(torch.randn(N, E, device="cuda"), dim=1)
+    with EmbeddingIndex(E, N) as ix:
+        ix.add_device(g.data_ptr(), N, s)
+        for Q in Qs:
+            for size in sizes:
+                T = Q * size
+                t = torch.nn.functional.normalize(torch.randn(T, E, device="cuda"), dim=1)
+                lims = torch.arange(0, T + 1, size, dtype=torch.int32, device="cuda")
+                idx, sc = torch.empty((Q, k), dtype=torch.int64, device="cuda"), torch.empty((Q, k), device="cuda")
+                pi, ps = torch.empty((T, k), dtype=torch.int64, device="cuda"), torch.empty((T, k), device="cuda")
+                mat = torch.empty(T, N, device="cuda")
+                base = {}
+
+                def compound():
+                    ix.search_compound_device(t.data_ptr(), T, lims.data_ptr(), Q, k, "min", idx.data_ptr(), sc.data_ptr(),
+                                              100.0, 0.0, s, max_terms=size)
+
+                def matrix():
+                    _lib.check(L.clipgpu_similarity_device(ctypes.c_void_p(t.data_ptr()), T, ctypes.c_void_p(g.data_ptr()),
+                                                           N, E, 100.0, 0.0, 2, 1, ctypes.c_void_p(mat.data_ptr()),
+                                                           ctypes.c_void_p(s)))
+                    base["score"], base["idx"] = torch.topk(torch.amin(mat.view(Q, size, N), dim=1), k, dim=1)
+
+                legs = [("compound", compound), ("matrix_amin_topk", matrix),
+                        ("search_T_plain", lambda: ix.search_device(t.data_ptr(), T, k, pi.data_ptr(), ps.data_ptr(),
+                                                                    100.0, 0.0, s))]
+                ms = {name: [] for name, _ in legs}
+                for rnd in range(warmup + runs):
+                    r = rnd % len(legs)
+                    for name, fn in legs[r:] + legs[:r]:  # every leg follows every other equally often
+                        v = _event_ms(fn)
+                        if rnd >= warmup:
+                            ms[name].append(v)
+                _lib.check(L.clipgpu_test_clock_probe(None, 2000, ctypes.c_void_p(probe.data_ptr())))
+                ticks = probe.cpu().tolist()
+                b_idx, b_score = base["idx"].cpu().numpy(), base["score"].cpu().numpy() + np.float32(0.0)
+                order = np.lexsort((b_idx, -b_score.astype(np.float64)), axis=1)
+                b_idx, b_score = np.take_along_axis(b_idx, order, 1), np.take_along_axis(b_score, order, 1)
+                assert np.array_equal(sc.cpu().numpy().view(np.uint32), b_score.view(np.uint32))
+                assert np.array_equal(idx.cpu().numpy(), b_idx)
+                out = {"measure": "topk_compound", "Q": Q, "terms_per_query": size, "T": T, "k": k, "N": N, "E": E,
+                       "runs": runs, "same_as_matrix_path": True, "matrix_bytes": T * N * 4,
+                       "sclk_after_mhz": round(100.0 * ticks[0] / ticks[1], 1) if ticks[1] > 0 else None}
+                for name, v in ms.items():
+                    out[name] = _stats(v, N * E * 4)
+                out["compound_over_matrix"] = round(out["compound"]["ms_median"] / out["matrix_amin_topk"]["ms_median"], 3)
+                out["compound_over_plain"] = round(out["compound"]["ms_median"] / out["search_T_plain"]["ms_median"], 3)
+                print(json.dumps(out), flush=True)
+
+
 def topk_routes_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 2, 4, 8, 12, 16)):
     """The measurement kNarrowRows (csrc/kernels/kernels.hpp) is set by: for every query count the
     few-query kernel can take, that kernel (route 2) against the wide one (route 1) on an f32 gallery,
@@ -922,6 +986,8 @@ if __name__ == "__main__":
         topk_range_leg()
     if "topkdeep" in which:  # the deep search (k up to 4096) against similarity + torch.topk, search k = 128, one range scan
         topk_deep_leg()
+    if "topkcompound" in which:  # compound queries against similarity + amin + topk, and against T plain searches
+        topk_compound_leg()
     if "kmeans" in which:  # one k-means iteration: assign against the range search, the integer-sum update
         kmeans_leg()
     if "ivf" in which:  # the probed search against the plain search on a clustered gallery
