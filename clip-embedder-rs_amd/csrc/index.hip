@@ -56,6 +56,13 @@
 // terms, scored by the smallest or the largest of its term logits.  The same chunks of 256 queries; per chunk a
 // gather pads the groups to the chunk's slot width into a buffer of the handle's (lazy, as the deep search's),
 // the compound phase 1 fills the search workspace and the search's merge writes the result.
+//
+// Group labels and the grouped search (clipgpu_index_set_groups, clipgpu_index_groups,
+// clipgpu_index_search_grouped[_device]; kernels/grouped.hip).  One uint32 label per slot of the capacity and,
+// behind them, the host form's staged groups: one buffer, allocated and filled with "ungrouped" at the first
+// set_groups or grouped search and kept until the handle is destroyed; an index that never calls either has none.
+// add leaves new rows ungrouped, set_rows and remove keep a slot's label, clear resets every label.  A grouped
+// search is the same chunks of 256 queries, the compound search's span cut at width 1, one launch_grouped each.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -144,6 +151,8 @@ struct clipgpu_index {
   char* dp_work = nullptr;       // the deep search: what deep_buffers carves; lazy, kept until the handle is destroyed
   char* cp_work = nullptr;       // compound queries: what compound_buffers places; lazy, kept likewise
   int64_t cp_work_n = 0;
+  char* gp_labels = nullptr;     // group labels uint32 [capacity], then the host form's staged groups int64
+                                 // [kQueryChunk][kTopkMax]; lazy, kept likewise; NULL = every row ungrouped
   hipStream_t stream = nullptr;  // the host-buffer forms' stream
   hipEvent_t done = nullptr;     // recorded after every device-side operation
 };
@@ -896,9 +905,146 @@ int compound_host(clipgpu_index* ix, const CompoundReq& r, const int64_t* lims, 
   });
 }
 
+// ---- group labels and the grouped search (kernels/grouped.hip) ----------------------------------------------
+size_t group_label_bytes(const clipgpu_index* ix) { return align256((size_t)ix->capacity * 4); }
+int64_t* staged_groups(clipgpu_index* ix) { return (int64_t*)(ix->gp_labels + group_label_bytes(ix)); }
+
+// The labels, allocated and filled with "ungrouped" at the first use (synchronous, once per handle); a failed
+// allocation is CLIPGPU_ERR_DEVICE and leaves the handle without them, usable.  Callers hold the mutex.
+uint32_t* group_labels(clipgpu_index* ix) {
+  if (!ix->gp_labels) {
+    char* p = nullptr;
+    HIP_CHECK(hipMalloc((void**)&p, group_label_bytes(ix) + (size_t)kQueryChunk * kTopkMax * 8));
+    hipError_t err = launch_group_fill((uint32_t*)p, 0, (long)ix->capacity, ix->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(ix->stream);
+    if (err != hipSuccess) {
+      (void)hipFree(p);
+      HIP_CHECK(err);
+    }
+    ix->gp_labels = p;
+  }
+  return (uint32_t*)ix->gp_labels;
+}
+
+struct GroupedOut { int64_t* idx; float* score; int64_t* group; };
+
+// Searches the device rows r.q in chunks of kQueryChunk rows on `s`, all under one mask, into the device buffers
+// of `o`.  The span cut is the compound search's at width 1: one-wave blocks over (query tiles, spans), such that
+// the workspace holds a chunk's rows.
+void grouped_on(clipgpu_index* ix, const SearchReq& r, const uint32_t* mask, const uint32_t* labels, const GroupedOut& o,
+                hipStream_t s) {
+  for (int64_t q0 = 0; q0 < r.nq; q0 += kQueryChunk) {
+    const int rows = (int)std::min(kQueryChunk, r.nq - q0);
+    const TopkPlan p = compound_plan(ix->size, rows, 1, ix->ws_blocks);
+    HIP_CHECK(launch_grouped({r.q + q0 * ix->E, rows, ix->gallery, ix->dtype, (int)ix->size, (int)ix->E, r.scale, r.bias,
+                              (int)r.k, p, ix->d_ws, mask, labels, o.idx + q0 * r.k, o.score + q0 * r.k,
+                              o.group ? o.group + q0 * r.k : nullptr, s}));
+  }
+  mark_last(ix, s);
+}
+
+int grouped_device(clipgpu_index* ix, const SearchReq& r, const GroupedOut& o, hipStream_t s) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_search(ix, r, {o.idx, o.score, nullptr, nullptr});
+    if ((uintptr_t)r.q & 15) throw ClipErr(CLIPGPU_ERR_INVALID, "d_queries must be 16-byte aligned");
+    const uint32_t* labels = group_labels(ix);
+    order_after_last(ix, s);
+    grouped_on(ix, r, build_mask(ix, r.allow, s), labels, o, s);
+  });
+}
+
+int grouped_host(clipgpu_index* ix, const SearchReq& r, const GroupedOut& o) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_search(ix, r, {o.idx, o.score, nullptr, nullptr});
+    HIP_CHECK(hipEventSynchronize(ix->done));  // the staging buffers and the filter area are free
+    const uint32_t* labels = group_labels(ix);
+    if (r.allow) HIP_CHECK(copy_h2d(ix->d_eff, r.allow, (size_t)live_words(ix->size) * 4));
+    const uint32_t* mask = build_mask(ix, r.allow ? ix->d_eff : nullptr, ix->stream);
+    const GroupedOut st = {ix->st_idx, ix->st_score, o.group ? staged_groups(ix) : nullptr};
+    for (int64_t q0 = 0; q0 < r.nq; q0 += kQueryChunk) {
+      const SearchReq c = {ix->st_q, std::min(kQueryChunk, r.nq - q0), r.k, r.scale, r.bias, TOPK_PROBS_NONE, nullptr};
+      HIP_CHECK(copy_h2d(ix->st_q, r.q + q0 * ix->E, (size_t)c.nq * ix->E * 4));
+      grouped_on(ix, c, mask, labels, st, ix->stream);
+      HIP_CHECK(hipStreamSynchronize(ix->stream));
+      HIP_CHECK(copy_d2h(o.idx + q0 * r.k, st.idx, (size_t)c.nq * r.k * 8));
+      HIP_CHECK(copy_d2h(o.score + q0 * r.k, st.score, (size_t)c.nq * r.k * 4));
+      if (st.group) HIP_CHECK(copy_d2h(o.group + q0 * r.k, st.group, (size_t)c.nq * r.k * 8));
+    }
+  });
+}
+
 }  // namespace
 
 extern "C" {
+
+int clipgpu_index_set_groups(clipgpu_index* ix, const int64_t* ids, const int32_t* groups, int64_t n) {
+  return guarded([&]() {
+    check_ids(ix, ids, n);
+    if (!groups && n > 0) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    check_ids_in_range(ix, ids, n);  // before any change and any device work
+    for (int64_t i = 0; i < n; ++i)
+      if (groups[i] < -1)
+        throw ClipErr(CLIPGPU_ERR_INVALID, "a group label must be in 0..2147483647, or -1 for no group, got " +
+                                               std::to_string(groups[i]));
+    std::vector<int64_t> sorted(ids, ids + n);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) throw ClipErr(CLIPGPU_ERR_INVALID, "duplicate id");
+    if (n == 0) return;
+    HIP_CHECK(hipSetDevice(ix->device));
+    HIP_CHECK(hipEventSynchronize(ix->done));
+    uint32_t* labels = group_labels(ix);
+    // the ids and, behind them, their labels go through the scratch, in pieces of at most 2^20 rows
+    const int64_t piece = std::min<int64_t>(n, 1 << 20);
+    char* d = (char*)scratch_bytes(ix, (size_t)piece * 12);
+    for (int64_t r0 = 0; r0 < n; r0 += piece) {
+      const int64_t m = std::min(piece, n - r0);
+      HIP_CHECK(copy_h2d(d, ids + r0, (size_t)m * 8));
+      HIP_CHECK(copy_h2d(d + piece * 8, groups + r0, (size_t)m * 4));
+      HIP_CHECK(launch_group_set((const int64_t*)d, (const int32_t*)(d + piece * 8), (long)m, labels, (long)ix->size,
+                                 ix->stream));
+      HIP_CHECK(hipStreamSynchronize(ix->stream));
+    }
+    mark_last(ix, ix->stream);
+  });
+}
+
+int clipgpu_index_groups(clipgpu_index* ix, int32_t* out) {
+  return guarded([&]() {
+    if (!ix || !out) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    if (ix->size == 0) return;
+    if (!ix->gp_labels) {  // never labelled: nothing to read
+      std::fill(out, out + ix->size, -1);
+      return;
+    }
+    HIP_CHECK(hipSetDevice(ix->device));
+    HIP_CHECK(hipEventSynchronize(ix->done));
+    HIP_CHECK(copy_d2h(out, ix->gp_labels, (size_t)ix->size * 4));
+    for (int64_t i = 0; i < ix->size; ++i)
+      if (out[i] < 0) out[i] = -1;  // 0x80000000 | slot
+  });
+}
+
+int clipgpu_index_search_grouped(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, float logit_scale,
+                                 float logit_bias, const uint32_t* allow, int64_t* out_idx, float* out_score,
+                                 int64_t* out_group) {
+  return grouped_host(ix, {queries, nq, k, logit_scale, logit_bias, TOPK_PROBS_NONE, allow}, {out_idx, out_score, out_group});
+}
+
+int clipgpu_index_search_grouped_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k,
+                                        float logit_scale, float logit_bias, const uint32_t* d_allow, int64_t* d_idx,
+                                        float* d_score, int64_t* d_group, void* stream) {
+  return grouped_device(ix, {d_queries, nq, k, logit_scale, logit_bias, TOPK_PROBS_NONE, d_allow}, {d_idx, d_score, d_group},
+                        (hipStream_t)stream);
+}
+
+int clipgpu_test_grouped_collapse(int mode) {
+  return guarded([&]() {
+    if (mode < 0 || mode > 2) throw ClipErr(CLIPGPU_ERR_INVALID, "mode must be 0 (default), 1 (collapse on) or 2 (collapse off)");
+    g_grouped_collapse.store(mode);
+  });
+}
 
 int clipgpu_index_search_compound(clipgpu_index* ix, const float* terms, int64_t n_terms, const int64_t* lims,
                                   int64_t nq, int64_t k, int op, float logit_scale, float logit_bias,
@@ -1241,6 +1387,7 @@ void clipgpu_index_destroy(clipgpu_index* ix) {
   if (ix->cd_work) (void)hipFree(ix->cd_work);
   if (ix->dp_work) (void)hipFree(ix->dp_work);
   if (ix->cp_work) (void)hipFree(ix->cp_work);
+  if (ix->gp_labels) (void)hipFree(ix->gp_labels);
   if (ix->work) (void)hipFree(ix->work);
   if (ix->gallery) (void)hipFree(ix->gallery);
   delete ix;
@@ -1256,6 +1403,12 @@ int clipgpu_index_clear(clipgpu_index* ix) {
   return guarded([&]() {
     if (!ix) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
     std::lock_guard<std::mutex> lk(ix->mu);
+    if (ix->gp_labels && ix->size > 0) {  // every label back to "ungrouped", behind the last search
+      HIP_CHECK(hipSetDevice(ix->device));
+      HIP_CHECK(hipEventSynchronize(ix->done));
+      HIP_CHECK(launch_group_fill((uint32_t*)ix->gp_labels, 0, (long)ix->size, ix->stream));
+      mark_last(ix, ix->stream);
+    }
     ix->size = 0;  // a later add overwrites the rows only after the last search (the `done` event)
     ix->pt_stale = true;
     ix->h_live = std::vector<uint32_t>();  // every future row is live

@@ -283,6 +283,41 @@ struct CompoundArgs {
 };
 hipError_t launch_compound(const CompoundArgs& a);
 
+// Grouped search (kernels/grouped.hip): every gallery row has a group label, and per query row the result is the
+// first k group representatives -- a group's representative being its first row in launch_topk's order over the
+// rows mask allows -- as out_idx / out_score [nq][k] in launch_topk's form (its score bits; (-1, -inf) beyond the
+// groups there are) and out_group int64 [nq][k] (NULL = not wanted): the label, -1 for an ungrouped row or an
+// empty slot.  labels: uint32 [at least N], a caller's label below 2^31 or 0x80000000 | slot for a row without
+// one (launch_group_fill writes those for slots [first, first + n); launch_group_set writes labels[ids[i]] =
+// groups[i], or the ungrouped value where groups[i] < 0, skipping an id outside [0, slots)).  One call is a phase 1
+// of one-wave blocks over (16-row query tiles, spans) into ws and its own merge; any nq; the plan is
+// compound_plan(N, nq, 1, ...).  q 16-byte aligned.  Runs of equal adjacent labels are collapsed in registers
+// before the selection (the result never depends on it): g_grouped_collapse (clipgpu_test_grouped_collapse)
+// 0 = kGroupedCollapseDefault, 1 = on, 2 = off.
+constexpr bool kGroupedCollapseDefault = true;
+extern std::atomic<int> g_grouped_collapse;
+bool grouped_collapse();
+hipError_t launch_group_fill(uint32_t* labels, long first, long n, hipStream_t s);
+hipError_t launch_group_set(const int64_t* ids, const int32_t* groups, long n, uint32_t* labels, long slots,
+                            hipStream_t s);
+struct GroupedArgs {
+  const float* q;  // [nq][E]
+  int nq;
+  const void* g;  // [N][E] of dtype (TopkGal)
+  int dtype, N, E;
+  float scale, bias;
+  int k;
+  TopkPlan plan;
+  void* ws;
+  const uint32_t* mask;
+  const uint32_t* labels;
+  int64_t* out_idx;
+  float* out_score;
+  int64_t* out_group;
+  hipStream_t stream;
+};
+hipError_t launch_grouped(const GroupedArgs& a);
+
 // Inverted lists (kernels/lists.hip): the CSR of the rows by label.  label: int32 [N], -1 = not in any list,
 // else below C (1 <= C <= kClusterMaxCentroids).  offsets int32 [C + 1]: offsets[c] = the rows with a label
 // below c; ids int32 [offsets[C]]: the rows of list c at [offsets[c], offsets[c + 1]), ascending -- a pure

@@ -117,6 +117,12 @@ _PROTOS = [
                                               c_float, c_void_p, c_void_p, c_void_p]),
     ("clipgpu_index_search_compound_device", c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64,
                                                      c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("clipgpu_index_set_groups", c_int, [c_void_p, c_void_p, c_void_p, c_int64]),
+    ("clipgpu_index_groups", c_int, [c_void_p, c_void_p]),
+    ("clipgpu_index_search_grouped", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_void_p, c_void_p,
+                                             c_void_p, c_void_p]),
+    ("clipgpu_index_search_grouped_device", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_void_p,
+                                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     ("clipgpu_comm_unique_id", c_int, [c_void_p]),
     ("clipgpu_comm_init_rank", c_int, [c_void_p, c_void_p, c_int, c_int]),
     ("clipgpu_comm_info", c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
@@ -144,6 +150,7 @@ _PROTOS = [
     ("clipgpu_test_probe_chunk", c_int, [c_int]),
     ("clipgpu_test_codes_stage", c_int, [c_int]),
     ("clipgpu_test_deep_cand", c_int, [c_int]),
+    ("clipgpu_test_grouped_collapse", c_int, [c_int]),
     ("clipgpu_test_index_kmeans_sums", c_int, [c_void_p, c_int64, c_void_p, POINTER(c_int)]),
     ("clipgpu_test_index_kmeans_update", c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     ("clipgpu_test_gemm_lnf", c_int, [c_int, c_int, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,

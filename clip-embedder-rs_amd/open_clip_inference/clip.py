@@ -122,15 +122,20 @@ class Clip:
         return out
 
     # -- a gallery resident on the GPU, searched top-k (README.md:76-82, examples/search.rs) ----
-    def build_index(self, images, capacity=None, dtype="f32"):
+    def build_index(self, images, capacity=None, dtype="f32", groups=None):
         """Embeds ``images`` and stores them in an ``EmbeddingIndex`` on the vision engine's first
         device (``capacity`` rows, default: as many as there are images; ``dtype`` "f32", "f16" or
-        "bf16": the index's storage type); image i is index i."""
+        "bf16": the index's storage type); image i is index i.  ``groups`` (None: every row ungrouped) is one
+        group label per image, for ``search_grouped``: the video of a frame, the picture of a crop."""
         from .index import EmbeddingIndex
         embs = self.vision.embed_images(images)
+        if groups is not None and len(groups) != len(embs):
+            raise ValueError(f"{len(groups)} groups for {len(embs)} images")
         index = EmbeddingIndex(embs.shape[1], len(embs) if capacity is None else int(capacity),
                                self.vision.session.devices[0], dtype)
         index.add(embs)
+        if groups is not None:
+            index.set_groups(np.arange(len(embs)), groups)
         return index
 
     def search(self, index, texts: Sequence[str], k: int, allow=None, nprobe=None, refine=None
@@ -165,6 +170,17 @@ class Clip:
         scale, bias = self._scale_bias()
         idx, score = index.search_deep(self.text.embed_texts(texts), k, float(scale), float(bias), allow=allow)
         return [[(int(i), float(s)) for i, s in zip(ri, rs) if i >= 0] for ri, rs in zip(idx, score)]
+
+    def search_grouped(self, index, texts: Sequence[str], k: int, allow=None) -> List[List[Tuple[int, float, int]]]:
+        """``search`` with distinct results per group: per text the k best GROUPS of ``index`` (the labels of
+        ``build_index(groups=)`` or ``EmbeddingIndex.set_groups``), each by its best row, as (gallery index,
+        logit, group label), best first; the label is -1 for a row without one, which is a group of its own
+        (``EmbeddingIndex.search_grouped``)."""
+        scale, bias = self._scale_bias()
+        idx, score, group = index.search_grouped(self.text.embed_texts(texts), k, float(scale), float(bias), allow=allow,
+                                                 return_groups=True)
+        return [[(int(i), float(s), int(g)) for i, s, g in zip(ri, rs, rg) if i >= 0]
+                for ri, rs, rg in zip(idx, score, group)]
 
     def _search_groups(self, index, groups, k: int, op: str, allow) -> List[List[Tuple[int, float]]]:
         groups = [list(g) for g in groups]

@@ -16,6 +16,7 @@ TOPK_MAX = 128  # CLIPGPU_TOPK_MAX
 DEEP_K_MAX = 4096  # CLIPGPU_DEEP_K_MAX: the largest k of search_deep
 COMPOUND_TERMS_MAX = 16  # CLIPGPU_COMPOUND_TERMS_MAX: the most terms of one compound query
 COMPOUND_OPS = {"min": 0, "max": 1}  # CLIPGPU_COMPOUND_MIN (all-of), CLIPGPU_COMPOUND_MAX (any-of)
+GROUP_MAX = (1 << 31) - 1  # the largest group label of set_groups (include/clipgpu.h)
 RANGE_MAX = 1 << 28  # most records of a range search or a self-join (include/clipgpu.h)
 MAX_CENTROIDS = 1 << 16  # most centroids of assign and kmeans (include/clipgpu.h)
 CODES_MAX_E = 1024  # the widest rows enable_codes takes (include/clipgpu.h)
@@ -59,7 +60,8 @@ class EmbeddingIndex:
     them), and ``search(..., allow=)`` searches a subset, exactly.  ``search_probs`` is the same search
     with the softmax (over all searched rows) or sigmoid probabilities of the k results.  ``search_deep`` is
     ``search`` for k up to 4096, as exact.  ``search_compound`` takes queries made of up to 16 terms and scores a
-    row by the smallest (all-of) or largest (any-of) of its term logits, in one scan.  ``range_search``
+    row by the smallest (all-of) or largest (any-of) of its term logits, in one scan.  ``set_groups`` labels rows
+    and ``search_grouped`` returns the k best groups, each by its best row.  ``range_search``
     returns every row at or above a score threshold instead of the k best, and ``duplicates`` joins the
     gallery against itself at a threshold; neither builds the score matrix.  ``assign`` gives every row its
     nearest of C centroids and ``kmeans`` puts the rows into groups, reproducibly.  ``partition`` cuts the
@@ -312,6 +314,72 @@ class EmbeddingIndex:
                                                          int(nq), int(max_terms), k, opv, float(logit_scale),
                                                          float(logit_bias), c_void_p(d_allow or None), c_void_p(d_idx),
                                                          c_void_p(d_score), c_void_p(stream or None)))
+
+    # ---- group labels and the grouped search ------------------------------------------------------------
+    def set_groups(self, ids, groups) -> None:
+        """Gives the rows at ``ids`` (each < len(self), none twice) the group labels ``groups``: integers in
+        [0, 2^31), or -1 to make a row ungrouped again.  A row that never got a label is ungrouped, a group of
+        its own.  ``add`` leaves new rows ungrouped; ``set_rows`` and ``remove`` keep a slot's label, so a reused
+        slot belongs to its old group until ``set_groups`` says otherwise; ``clear`` resets every label.  A bad
+        id or label raises and changes nothing.  The first call allocates 4 bytes per slot of the capacity."""
+        x = self._ids(ids)
+        g = np.atleast_1d(np.asarray(groups))
+        if g.ndim != 1 or (g.size and not np.issubdtype(g.dtype, np.integer)):
+            raise TypeError("groups must be a 1-d array of integers")
+        if g.size != x.size:
+            from .error import ShapeError
+            raise ShapeError(f"Shape error: {x.size} ids for {g.size} groups")
+        if g.size and (int(g.min()) < -1 or int(g.max()) > GROUP_MAX):
+            raise ValueError(f"a group label must be in 0..{GROUP_MAX}, or -1 for no group, got "
+                             f"{int(g.min())} to {int(g.max())}")
+        g = np.ascontiguousarray(g, dtype=np.int32)
+        check(lib().clipgpu_index_set_groups(self.handle, x.ctypes.data, g.ctypes.data, x.size))
+
+    def groups(self) -> np.ndarray:
+        """The group labels, int64 [len(self)]: -1 for an ungrouped row."""
+        out = np.empty(len(self), np.int32)
+        check(lib().clipgpu_index_groups(self.handle, out.ctypes.data))
+        return out.astype(np.int64)
+
+    @staticmethod
+    def _grouped_k(k) -> int:
+        """k, checked before any native call."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"k must be an integer, got {type(k).__name__}")
+        if not 1 <= int(k) <= TOPK_MAX:
+            raise ValueError(f"k must be in 1..{TOPK_MAX}, got {int(k)}")
+        return int(k)
+
+    def search_grouped(self, queries, k: int, logit_scale: float = 1.0, logit_bias: float = 0.0, allow=None,
+                       return_groups: bool = False):
+        """The k best GROUPS per query, each by its best row (field collapsing, group-by search): over a gallery
+        of video frames, the k best videos with the best frame of each, where ``search`` would return k frames of
+        one video.  Take the live allowed rows in ``search``'s order; a group's representative is its first row
+        in that order, and the result is the first k representatives: (indices int64 [nq, k], scores f32 [nq, k])
+        with ``search``'s score bits, (-1, -inf) beyond the groups that have a live allowed row.
+        ``return_groups=True`` adds int64 [nq, k], the label of each result, -1 for an ungrouped row or an empty
+        slot.  Exact: an index without labels returns what ``search`` returns, and removing or filtering out a
+        group's best row makes its next best row the representative.  1 <= k <= 128."""
+        k = self._grouped_k(k)
+        words = self._allow_words(allow)
+        q = self._rows(queries, "queries")
+        idx = np.empty((q.shape[0], k), np.int64)
+        score = np.empty((q.shape[0], k), np.float32)
+        group = np.empty((q.shape[0], k), np.int64) if return_groups else None
+        check(lib().clipgpu_index_search_grouped(self.handle, q.ctypes.data, q.shape[0], k, float(logit_scale),
+                                                 float(logit_bias), None if words is None else words.ctypes.data,
+                                                 idx.ctypes.data, score.ctypes.data,
+                                                 None if group is None else group.ctypes.data))
+        return (idx, score, group) if return_groups else (idx, score)
+
+    def search_grouped_device(self, d_queries: int, nq: int, k: int, d_idx: int, d_score: int, logit_scale: float = 1.0,
+                              logit_bias: float = 0.0, stream: int = 0, d_allow: int = 0, d_group: int = 0) -> None:
+        """``search_grouped`` on device pointers (as ``search_device``, queries 16-byte aligned; ``d_group`` int64
+        [nq, k] out or 0 = not wanted), ordered on ``stream``; returns without synchronising."""
+        check(lib().clipgpu_index_search_grouped_device(self.handle, c_void_p(d_queries), int(nq), self._grouped_k(k),
+                                                        float(logit_scale), float(logit_bias),
+                                                        c_void_p(d_allow or None), c_void_p(d_idx), c_void_p(d_score),
+                                                        c_void_p(d_group or None), c_void_p(stream or None)))
 
     @staticmethod
     def _range_args(threshold, limit, what: str) -> Tuple[float, int]:

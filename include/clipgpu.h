@@ -640,6 +640,44 @@ int clipgpu_index_search_compound_device(clipgpu_index* ix, const float* d_terms
                                          float logit_scale, float logit_bias, const uint32_t* d_allow,
                                          int64_t* d_idx, float* d_score, void* stream);
 
+/* ---- grouped search: the k best groups, each by its best row -------------------------------------------------
+ * A gallery is rarely one row per thing: a video is hundreds of frames, a picture several crops.  Every row has
+ * a group label, an integer in [0, 2^31) set by the caller; a row that never got one is UNGROUPED, a group of
+ * its own.  For a query take the live allowed rows in clipgpu_index_search's order (descending score, then
+ * ascending row); a group's REPRESENTATIVE is its first row in that order, and the result is the first k
+ * representatives: out_idx int64 [nq][k], out_score f32 [nq][k] with the search's bits (nothing canonicalised),
+ * out_group int64 [nq][k] (may be NULL) the label, -1 for an ungrouped row; (-1, -inf, -1) beyond the number of
+ * groups that have a live allowed row.  Exact and bit-reproducible: neither the [nq][size] matrix nor a deep
+ * list that one long group could fill is built; the kernels keep one entry per group in their lists
+ * (kernels/grouped.hip; DESIGN.md, embedding index, grouped search).  So an index in which no row is labelled
+ * returns what clipgpu_index_search returns, bit for bit, and removing or filtering out a group's best row makes
+ * its next best row the representative.  1 <= k <= CLIPGPU_TOPK_MAX; `allow`, removed rows and the three storage
+ * types as in the filtered search.  Not offered: more than one row per group, k above 128, and grouped forms of
+ * the probability, deep, probed, coded and compound searches.
+ * clipgpu_index_set_groups overwrites the labels of rows ids[0 .. n) with groups[0 .. n); a label of -1 makes the
+ * row ungrouped again.  It runs on the index's stream, ordered like clipgpu_index_set_rows.  clipgpu_index_groups
+ * exports the labels of rows [0, size), -1 for an ungrouped row.  clipgpu_index_add[_device] leaves new rows
+ * ungrouped; clipgpu_index_set_rows and clipgpu_index_remove KEEP a slot's label -- a reused slot belongs to its
+ * old group until clipgpu_index_set_groups says otherwise; clipgpu_index_clear resets every label.
+ * Storage: 4 bytes per slot of the capacity (and 256 KiB of staging), allocated at the first
+ * clipgpu_index_set_groups or grouped search and kept until the handle is destroyed (a failed allocation is
+ * CLIPGPU_ERR_DEVICE and leaves the index usable); an index that uses neither allocates nothing.
+ * The _device form: d_queries (16-byte aligned), d_allow, d_idx, d_score, d_group on the device, ordered on
+ * `stream` behind the handle's last operation on any stream, no synchronisation (the first use of the labels
+ * allocates, which synchronises once).  Mutex, event ordering, chunking and host staging are those of the other
+ * searches.
+ * Refused with CLIPGPU_ERR_INVALID before any device call: a NULL argument; nq <= 0 or an empty index ("Empty
+ * batch"); k outside 1 .. CLIPGPU_TOPK_MAX; (set_groups) an id outside [0, size), a repeated id, a label below -1
+ * (the message names the range 0..2147483647).  A refused set_groups changes nothing. */
+int clipgpu_index_set_groups(clipgpu_index* ix, const int64_t* ids, const int32_t* groups, int64_t n);
+int clipgpu_index_groups(clipgpu_index* ix, int32_t* out);
+int clipgpu_index_search_grouped(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, float logit_scale,
+                                 float logit_bias, const uint32_t* allow, int64_t* out_idx, float* out_score,
+                                 int64_t* out_group);
+int clipgpu_index_search_grouped_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k,
+                                        float logit_scale, float logit_bias, const uint32_t* d_allow, int64_t* d_idx,
+                                        float* d_score, int64_t* d_group, void* stream);
+
 /* ---- data-parallel sharding + the RCCL all-gather (north_star: "batches shard
  * data-parallel across the 8 GPUs of one node with an RCCL all-gather over xGMI only for the final
  * embedding matrix").  The reference has no multi-device path: embed_images / embed_texts

@@ -313,6 +313,11 @@ int clipgpu_test_codes_stage(int stage);
  * capacity is max(k, n): with n = 1 the select resolves all the way to the k-th key, so a small gallery walks
  * every digit.  The result never depends on it; the pass counts do. */
 int clipgpu_test_deep_cand(int n);
+/* Whether phase 1 of a grouped search (clipgpu_index_search_grouped[_device]) collapses runs of equal adjacent
+ * labels in registers before its selection, process-wide and atomic, for every grouped search started
+ * afterwards: 0 = the default (on), 1 = on, 2 = off.  Other values are refused.  The result never depends on it;
+ * tests run both forms on one input and the benchmark times them in one process. */
+int clipgpu_test_grouped_collapse(int mode);
 
 #ifdef __cplusplus
 }

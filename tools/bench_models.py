@@ -756,6 +756,82 @@ def topk_compound_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 16, 256),
                 print(json.dumps(out), flush=True)
 
 
+def topk_grouped_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 16, 256), centres=1024, sigma=0.05):
+    """The grouped search (search_grouped_device) over an f32 gallery whose rows lie centre by centre (N / centres
+    adjacent rows around each of `centres` unit vectors; a query is a fresh draw around one centre, so its hits are
+    adjacent rows).  Labelings: every row ungrouped; adjacent runs of 16 and of 256 (a query's hits concentrate in
+    few groups: the case the in-register collapse is for); scattered labels j % 1000; seven labels j % 7 (fewer
+    groups than k: the threshold never rises).  Per (labeling, Q), legs alternating in one process (rotating order,
+    device-event timings after `warmup` rounds): the grouped search with the collapse on and off
+    (clipgpu_test_grouped_collapse); search_device at the same k; and the matrix path -- clipgpu_similarity_device
+    logits into a [Q][N] tensor (its bytes are reported), scatter_reduce(amax) per group, torch.topk.  The grouped
+    scores are checked against the matrix path's, bit for bit, and the two collapse forms against each other."""
+    import ctypes
+    from open_clip_inference import EmbeddingIndex
+    torch.manual_seed(0)
+    L = _lib.lib()
+    s = torch.cuda.current_stream().cuda_stream
+    cen0 = torch.nn.functional.normalize(torch.randn(centres, E, device="cuda"), dim=1)
+    j = torch.arange(N, device="cuda")
+    g = torch.nn.functional.normalize(cen0[j // (N // centres)] + sigma * torch.randn(N, E, device="cuda"), dim=1).contiguous()
+    labelings = (("ungrouped", None), ("runs16", j // 16), ("runs256", j // 256), ("mod1000", j % 1000), ("mod7", j % 7))
+    with EmbeddingIndex(E, N) as ix:
+        ix.add_device(g.data_ptr(), N, s)
+        for lname, lab in labelings:
+            ids = np.arange(N)
+            ix.set_groups(ids, np.full(N, -1) if lab is None else lab.cpu().numpy())
+            n_groups = N if lab is None else int(lab.max()) + 1
+            kk = min(k, n_groups)
+            for Q in Qs:
+                q = torch.nn.functional.normalize(cen0[torch.randint(0, centres, (Q,), device="cuda")] +
+                                                  sigma * torch.randn(Q, E, device="cuda"), dim=1).contiguous()
+                mat = torch.empty(Q, N, device="cuda")
+                out_t = {m: (torch.empty((Q, k), dtype=torch.int64, device="cuda"), torch.empty((Q, k), device="cuda"))
+                         for m in (1, 2)}
+                pi, ps = torch.empty((Q, k), dtype=torch.int64, device="cuda"), torch.empty((Q, k), device="cuda")
+                base = {}
+
+                def grouped(mode):
+                    _lib.check(L.clipgpu_test_grouped_collapse(mode))
+                    ix.search_grouped_device(q.data_ptr(), Q, k, out_t[mode][0].data_ptr(), out_t[mode][1].data_ptr(),
+                                             100.0, 0.0, s)
+
+                def matrix():
+                    _lib.check(L.clipgpu_similarity_device(ctypes.c_void_p(q.data_ptr()), Q, ctypes.c_void_p(g.data_ptr()),
+                                                           N, E, 100.0, 0.0, 2, 1, ctypes.c_void_p(mat.data_ptr()),
+                                                           ctypes.c_void_p(s)))
+                    best = mat if lab is None else torch.full((Q, n_groups), float("-inf"), device="cuda").scatter_reduce(
+                        1, lab.expand(Q, N), mat, "amax")
+                    base["score"] = torch.topk(best, kk, dim=1)[0]
+
+                legs = [("grouped", lambda: grouped(1)), ("grouped_no_collapse", lambda: grouped(2)),
+                        ("plain_search", lambda: ix.search_device(q.data_ptr(), Q, k, pi.data_ptr(), ps.data_ptr(),
+                                                                  100.0, 0.0, s)),
+                        ("matrix_amax_topk", matrix)]
+                ms = {name: [] for name, _ in legs}
+                try:
+                    for rnd in range(warmup + runs):
+                        r = rnd % len(legs)
+                        for name, fn in legs[r:] + legs[:r]:  # every leg follows every other equally often
+                            v = _event_ms(fn)
+                            if rnd >= warmup:
+                                ms[name].append(v)
+                finally:
+                    _lib.check(L.clipgpu_test_grouped_collapse(0))
+                got = out_t[1][1].cpu().numpy()
+                assert np.array_equal(got[:, :kk].view(np.uint32), base["score"].cpu().numpy().view(np.uint32))
+                assert np.array_equal(got.view(np.uint32), out_t[2][1].cpu().numpy().view(np.uint32))
+                assert torch.equal(out_t[1][0], out_t[2][0])
+                out = {"measure": "topk_grouped", "labeling": lname, "groups": n_groups, "Q": Q, "k": k, "N": N, "E": E,
+                       "runs": runs, "same_scores_as_matrix_path": True, "matrix_bytes": Q * N * 4}
+                for name, v in ms.items():
+                    out[name] = _stats(v, N * E * 4)
+                out["grouped_over_plain"] = round(out["grouped"]["ms_median"] / out["plain_search"]["ms_median"], 3)
+                out["collapse_on_over_off"] = round(out["grouped"]["ms_median"] / out["grouped_no_collapse"]["ms_median"], 3)
+                out["grouped_over_matrix"] = round(out["grouped"]["ms_median"] / out["matrix_amax_topk"]["ms_median"], 3)
+                print(json.dumps(out), flush=True)
+
+
 def topk_routes_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 2, 4, 8, 12, 16)):
     """The measurement kNarrowRows (csrc/kernels/kernels.hpp) is set by: for every query count the
     few-query kernel can take, that kernel (route 2) against the wide one (route 1) on an f32 gallery,
@@ -988,6 +1064,8 @@ if __name__ == "__main__":
         topk_deep_leg()
     if "topkcompound" in which:  # compound queries against similarity + amin + topk, and against T plain searches
         topk_compound_leg()
+    if "topkgrouped" in which:  # the grouped search, collapse on and off, against the plain search and similarity + amax + topk
+        topk_grouped_leg()
     if "kmeans" in which:  # one k-means iteration: assign against the range search, the integer-sum update
         kmeans_leg()
     if "ivf" in which:  # the probed search against the plain search on a clustered gallery
