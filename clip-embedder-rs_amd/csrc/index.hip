@@ -63,6 +63,11 @@
 // set_groups or grouped search and kept until the handle is destroyed; an index that never calls either has none.
 // add leaves new rows ungrouped, set_rows and remove keep a slot's label, clear resets every label.  A grouped
 // search is the same chunks of 256 queries, the compound search's span cut at width 1, one launch_grouped each.
+//
+// Diversified search (clipgpu_index_search_diverse[_device]; kernels/diverse.hip): per chunk of 256 queries a
+// search for the pool of P candidates into an area of the handle's (or the caller's pool buffers), then
+// launch_diverse, which fills the chunk's Gram matrices [rows][P][P] behind the pool and selects.  The area is
+// lazy, grown when a call brings a larger P, kept until the handle is destroyed.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -153,6 +158,8 @@ struct clipgpu_index {
   int64_t cp_work_n = 0;
   char* gp_labels = nullptr;     // group labels uint32 [capacity], then the host form's staged groups int64
                                  // [kQueryChunk][kTopkMax]; lazy, kept likewise; NULL = every row ungrouped
+  char* dv_work = nullptr;       // the diversified search: what diverse_buffers places, for pools up to dv_work_n;
+  int64_t dv_work_n = 0;         // lazy, grown on demand, kept likewise
   hipStream_t stream = nullptr;  // the host-buffer forms' stream
   hipEvent_t done = nullptr;     // recorded after every device-side operation
 };
@@ -973,9 +980,103 @@ int grouped_host(clipgpu_index* ix, const SearchReq& r, const GroupedOut& o) {
   });
 }
 
+// ---- the diversified search (kernels/diverse.hip) ------------------------------------------------------------
+// What is asked beyond a SearchReq, and the optional pool outputs [nq][pool] (device or host, as the form's).
+struct DiverseReq { int64_t pool; float diversity; int64_t* pool_idx; float* pool_score; };
+// The regions of dv_work: a chunk's pool [kQueryChunk][kTopkMax] and its Gram matrices [kQueryChunk][P][P].
+struct DiverseWork { int64_t* idx; float* score; float* gram; };
+constexpr size_t kDiversePool = (size_t)kQueryChunk * kTopkMax;
+
+// The refusals of the pool and the diversity, after enter_search's; then the work area for pools of d.pool: grow,
+// the owner of the handle's lazy buffers, which frees a smaller area -- so a search in flight is waited for first.
+// A failed allocation is CLIPGPU_ERR_DEVICE and leaves the handle without the area, usable.  Callers hold the mutex.
+DiverseWork diverse_buffers(clipgpu_index* ix, const SearchReq& r, const DiverseReq& d) {
+  const std::string range = "1.." + std::to_string(CLIPGPU_TOPK_MAX);
+  if (d.pool < 1 || d.pool > CLIPGPU_TOPK_MAX)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "pool must be in " + range + ", got " + std::to_string(d.pool));
+  if (r.k > d.pool)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "k <= pool is required (pool in " + range + "), got k " + std::to_string(r.k) +
+                                           ", pool " + std::to_string(d.pool));
+  if (!(d.diversity >= 0.0f && d.diversity <= 1.0f))
+    throw ClipErr(CLIPGPU_ERR_INVALID, "diversity must be in [0, 1], got " + std::to_string(d.diversity));
+  if ((d.pool_idx == nullptr) != (d.pool_score == nullptr))
+    throw ClipErr(CLIPGPU_ERR_INVALID, "the pool outputs come as a pair: both or neither");
+  if (d.pool > ix->dv_work_n && ix->dv_work) HIP_CHECK(hipEventSynchronize(ix->done));
+  grow(ix->dv_work, ix->dv_work_n, d.pool, kDiversePool * 12 + (size_t)kQueryChunk * d.pool * d.pool * 4);
+  DiverseWork w;
+  w.idx = (int64_t*)ix->dv_work;
+  w.score = (float*)(ix->dv_work + kDiversePool * 8);
+  w.gram = (float*)(ix->dv_work + kDiversePool * 12);
+  return w;
+}
+
+// One chunk of `rows` device queries on `s`: the pool by the search's own launch (into pool_idx / pool_score,
+// [rows][pool]), then the re-ranking into d_idx / d_score [rows][k].  Stream order keeps the chunks of a call,
+// which share the Gram area, apart.
+void diverse_chunk(clipgpu_index* ix, const SearchReq& r, const float* d_q, int rows, const DiverseReq& d,
+                   const uint32_t* mask, int64_t* pool_idx, float* pool_score, float* gram, int64_t* d_idx,
+                   float* d_score, hipStream_t s) {
+  search_on(ix, {d_q, rows, d.pool, r.scale, r.bias, TOPK_PROBS_NONE, nullptr}, mask, {pool_idx, pool_score, nullptr, nullptr},
+            s);
+  HIP_CHECK(launch_diverse({ix->gallery, ix->dtype, (int)ix->size, (int)ix->E, rows, (int)d.pool, (int)r.k, r.scale, r.bias,
+                            d.diversity, pool_idx, pool_score, gram, d_idx, d_score, s}));
+  mark_last(ix, s);
+}
+
+int diverse_device(clipgpu_index* ix, const SearchReq& r, const DiverseReq& d, int64_t* d_idx, float* d_score,
+                   hipStream_t s) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_search(ix, r, {d_idx, d_score, nullptr, nullptr});
+    const DiverseWork w = diverse_buffers(ix, r, d);
+    order_after_last(ix, s);
+    const uint32_t* mask = build_mask(ix, r.allow, s);
+    for (int64_t q0 = 0; q0 < r.nq; q0 += kQueryChunk)  // the caller's pool buffers hold every chunk, the area one
+      diverse_chunk(ix, r, r.q + q0 * ix->E, (int)std::min(kQueryChunk, r.nq - q0), d, mask,
+                    d.pool_idx ? d.pool_idx + q0 * d.pool : w.idx, d.pool_score ? d.pool_score + q0 * d.pool : w.score,
+                    w.gram, d_idx + q0 * r.k, d_score + q0 * r.k, s);
+  });
+}
+
+int diverse_host(clipgpu_index* ix, const SearchReq& r, const DiverseReq& d, int64_t* out_idx, float* out_score) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_search(ix, r, {out_idx, out_score, nullptr, nullptr});
+    HIP_CHECK(hipEventSynchronize(ix->done));  // the staging buffers and the filter area are free
+    const DiverseWork w = diverse_buffers(ix, r, d);
+    if (r.allow) HIP_CHECK(copy_h2d(ix->d_eff, r.allow, (size_t)live_words(ix->size) * 4));
+    const uint32_t* mask = build_mask(ix, r.allow ? ix->d_eff : nullptr, ix->stream);
+    for (int64_t q0 = 0; q0 < r.nq; q0 += kQueryChunk) {
+      const int64_t rows = std::min(kQueryChunk, r.nq - q0);
+      HIP_CHECK(copy_h2d(ix->st_q, r.q + q0 * ix->E, (size_t)rows * ix->E * 4));
+      diverse_chunk(ix, r, ix->st_q, (int)rows, d, mask, w.idx, w.score, w.gram, ix->st_idx, ix->st_score, ix->stream);
+      HIP_CHECK(hipStreamSynchronize(ix->stream));
+      HIP_CHECK(copy_d2h(out_idx + q0 * r.k, ix->st_idx, (size_t)rows * r.k * 8));
+      HIP_CHECK(copy_d2h(out_score + q0 * r.k, ix->st_score, (size_t)rows * r.k * 4));
+      if (d.pool_idx) {
+        HIP_CHECK(copy_d2h(d.pool_idx + q0 * d.pool, w.idx, (size_t)rows * d.pool * 8));
+        HIP_CHECK(copy_d2h(d.pool_score + q0 * d.pool, w.score, (size_t)rows * d.pool * 4));
+      }
+    }
+  });
+}
+
 }  // namespace
 
 extern "C" {
+
+int clipgpu_index_search_diverse(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, int64_t pool,
+                                 float diversity, float logit_scale, float logit_bias, const uint32_t* allow,
+                                 int64_t* out_idx, float* out_score, int64_t* out_pool_idx, float* out_pool_score) {
+  return diverse_host(ix, {queries, nq, k, logit_scale, logit_bias, TOPK_PROBS_NONE, allow},
+                      {pool, diversity, out_pool_idx, out_pool_score}, out_idx, out_score);
+}
+
+int clipgpu_index_search_diverse_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k, int64_t pool,
+                                        float diversity, float logit_scale, float logit_bias, const uint32_t* d_allow,
+                                        int64_t* d_idx, float* d_score, int64_t* d_pool_idx, float* d_pool_score,
+                                        void* stream) {
+  return diverse_device(ix, {d_queries, nq, k, logit_scale, logit_bias, TOPK_PROBS_NONE, d_allow},
+                        {pool, diversity, d_pool_idx, d_pool_score}, d_idx, d_score, (hipStream_t)stream);
+}
 
 int clipgpu_index_set_groups(clipgpu_index* ix, const int64_t* ids, const int32_t* groups, int64_t n) {
   return guarded([&]() {
@@ -1388,6 +1489,7 @@ void clipgpu_index_destroy(clipgpu_index* ix) {
   if (ix->dp_work) (void)hipFree(ix->dp_work);
   if (ix->cp_work) (void)hipFree(ix->cp_work);
   if (ix->gp_labels) (void)hipFree(ix->gp_labels);
+  if (ix->dv_work) (void)hipFree(ix->dv_work);
   if (ix->work) (void)hipFree(ix->work);
   if (ix->gallery) (void)hipFree(ix->gallery);
   delete ix;

@@ -318,6 +318,28 @@ struct GroupedArgs {
 };
 hipError_t launch_grouped(const GroupedArgs& a);
 
+// Diversified re-ranking (kernels/diverse.hip): maximal marginal relevance over a pool of candidates per query.
+// pool_idx / pool_score [nq][P]: launch_topk's result for k = P (ids below N, (-1, -inf) padding at the end).
+// gram: work area, f32 [nq][P][P]; it receives G[t][u] = fmaf(row c[t] . row c[u], scale, bias), launch_similarity's
+// bits over the gallery's rows as stored, for the real candidates.  Step 0 takes candidate 0; step j >= 1 the open
+// real candidate with the best v = (1 - lam) l - lam m (each operation rounded once), m its largest G to a taken
+// candidate (-inf before any; a NaN never raises it), in topk_key.hpp's order on v, equal v by the lower pool
+// position.  out_idx / out_score [nq][k]: the taken candidates' ids and pool scores in that order, (-1, -inf) once
+// the real candidates are used up.  1 <= k <= P <= kTopkMax, 0 <= lam <= 1, nq <= 65535, E % 16 == 0.
+struct DiverseArgs {
+  const void* g;  // [N][E] of dtype (TopkGal)
+  int dtype, N, E;
+  int nq, P, k;
+  float scale, bias, lam;
+  const int64_t* pool_idx;
+  const float* pool_score;
+  float* gram;
+  int64_t* out_idx;
+  float* out_score;
+  hipStream_t stream;
+};
+hipError_t launch_diverse(const DiverseArgs& a);
+
 // Inverted lists (kernels/lists.hip): the CSR of the rows by label.  label: int32 [N], -1 = not in any list,
 // else below C (1 <= C <= kClusterMaxCentroids).  offsets int32 [C + 1]: offsets[c] = the rows with a label
 // below c; ids int32 [offsets[C]]: the rows of list c at [offsets[c], offsets[c + 1]), ascending -- a pure

@@ -123,6 +123,10 @@ _PROTOS = [
                                              c_void_p, c_void_p]),
     ("clipgpu_index_search_grouped_device", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_float, c_float, c_void_p,
                                                     c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("clipgpu_index_search_diverse", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_float, c_float,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("clipgpu_index_search_diverse_device", c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_float, c_float,
+                                                    c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("clipgpu_comm_unique_id", c_int, [c_void_p]),
     ("clipgpu_comm_init_rank", c_int, [c_void_p, c_void_p, c_int, c_int]),
     ("clipgpu_comm_info", c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),

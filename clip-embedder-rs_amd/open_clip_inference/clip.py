@@ -182,6 +182,17 @@ class Clip:
         return [[(int(i), float(s), int(g)) for i, s, g in zip(ri, rs, rg) if i >= 0]
                 for ri, rs, rg in zip(idx, score, group)]
 
+    def search_diverse(self, index, texts: Sequence[str], k: int, diversity: float = 0.5, pool=None, allow=None
+                       ) -> List[List[Tuple[int, float]]]:
+        """``search`` with variety: per text, k of its ``pool`` best rows (None: min(128, max(32, 4 k))) picked one
+        by one by maximal marginal relevance -- each the candidate with the best (1 - diversity) * logit -
+        diversity * (its largest similarity, in logit units, to a row already picked) -- as (gallery index, the
+        row's own logit) in the order picked (``EmbeddingIndex.search_diverse``)."""
+        scale, bias = self._scale_bias()
+        idx, score = index.search_diverse(self.text.embed_texts(texts), k, diversity, pool, float(scale), float(bias),
+                                          allow=allow)
+        return [[(int(i), float(s)) for i, s in zip(ri, rs) if i >= 0] for ri, rs in zip(idx, score)]
+
     def _search_groups(self, index, groups, k: int, op: str, allow) -> List[List[Tuple[int, float]]]:
         groups = [list(g) for g in groups]
         lims = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int64)

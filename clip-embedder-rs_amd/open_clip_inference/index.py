@@ -61,7 +61,8 @@ class EmbeddingIndex:
     with the softmax (over all searched rows) or sigmoid probabilities of the k results.  ``search_deep`` is
     ``search`` for k up to 4096, as exact.  ``search_compound`` takes queries made of up to 16 terms and scores a
     row by the smallest (all-of) or largest (any-of) of its term logits, in one scan.  ``set_groups`` labels rows
-    and ``search_grouped`` returns the k best groups, each by its best row.  ``range_search``
+    and ``search_grouped`` returns the k best groups, each by its best row.  ``search_diverse`` re-ranks a pool of
+    the best rows for variety (maximal marginal relevance), on the device.  ``range_search``
     returns every row at or above a score threshold instead of the k best, and ``duplicates`` joins the
     gallery against itself at a threshold; neither builds the score matrix.  ``assign`` gives every row its
     nearest of C centroids and ``kmeans`` puts the rows into groups, reproducibly.  ``partition`` cuts the
@@ -380,6 +381,60 @@ class EmbeddingIndex:
                                                         float(logit_scale), float(logit_bias),
                                                         c_void_p(d_allow or None), c_void_p(d_idx), c_void_p(d_score),
                                                         c_void_p(d_group or None), c_void_p(stream or None)))
+
+    # ---- the diversified search ---------------------------------------------------------------------------
+    @staticmethod
+    def _diverse_args(k, pool, diversity) -> Tuple[int, int, float]:
+        """(k, pool, diversity), checked before any native call; pool None: min(128, max(32, 4 k))."""
+        k = EmbeddingIndex._grouped_k(k)
+        if pool is None:
+            pool = min(TOPK_MAX, max(32, 4 * k))
+        if isinstance(pool, bool) or not isinstance(pool, (int, np.integer)):
+            raise TypeError(f"pool must be an integer, got {type(pool).__name__}")
+        if not 1 <= int(pool) <= TOPK_MAX:
+            raise ValueError(f"pool must be in 1..{TOPK_MAX}, got {int(pool)}")
+        if k > int(pool):
+            raise ValueError(f"k <= pool is required (pool in 1..{TOPK_MAX}), got k {k}, pool {int(pool)}")
+        lam = float(diversity)
+        if not 0.0 <= lam <= 1.0:  # a NaN fails both comparisons
+            raise ValueError(f"diversity must be in [0, 1], got {lam}")
+        return k, int(pool), lam
+
+    def search_diverse(self, queries, k: int, diversity: float = 0.5, pool=None, logit_scale: float = 1.0,
+                       logit_bias: float = 0.0, allow=None, return_pool: bool = False):
+        """``search`` with variety (maximal marginal relevance): over a library of bursts and re-saved copies, k
+        different pictures where ``search`` would return k of one scene.  The candidates are ``search(queries,
+        pool, ...)`` (``pool`` None: min(128, max(32, 4 k)); 1 <= k <= pool <= 128).  The first result is the best
+        candidate; each further one is the candidate with the best ``(1 - diversity) * logit - diversity * (its
+        largest logit-scaled similarity to a result already taken)`` in f32, ties by the position in the pool.
+        Returns (indices int64 [nq, k], scores f32 [nq, k]) in the order taken, each score the candidate's own
+        ``search`` logit, bit for bit; (-1, -inf) once the candidates are used up.  ``diversity`` 0 is ``search``,
+        1 is farthest-first.  ``return_pool=True`` adds (pool_idx [nq, pool], pool_scores [nq, pool]), the
+        candidates.  Gather, Gram matrix and selection run on the device (include/clipgpu.h has the exact rule)."""
+        k, pool, lam = self._diverse_args(k, pool, diversity)
+        words = self._allow_words(allow)
+        q = self._rows(queries, "queries")
+        idx = np.empty((q.shape[0], k), np.int64)
+        score = np.empty((q.shape[0], k), np.float32)
+        pidx = np.empty((q.shape[0], pool), np.int64) if return_pool else None
+        pscore = np.empty((q.shape[0], pool), np.float32) if return_pool else None
+        check(lib().clipgpu_index_search_diverse(self.handle, q.ctypes.data, q.shape[0], k, pool, lam, float(logit_scale),
+                                                 float(logit_bias), None if words is None else words.ctypes.data,
+                                                 idx.ctypes.data, score.ctypes.data,
+                                                 None if pidx is None else pidx.ctypes.data,
+                                                 None if pscore is None else pscore.ctypes.data))
+        return (idx, score, pidx, pscore) if return_pool else (idx, score)
+
+    def search_diverse_device(self, d_queries: int, nq: int, k: int, d_idx: int, d_score: int, diversity: float = 0.5,
+                              pool=None, logit_scale: float = 1.0, logit_bias: float = 0.0, stream: int = 0,
+                              d_allow: int = 0, d_pool_idx: int = 0, d_pool_score: int = 0) -> None:
+        """``search_diverse`` on device pointers (as ``search_device``; ``d_pool_idx`` int64 and ``d_pool_score``
+        f32 [nq, pool] out, both or 0 = not wanted), ordered on ``stream``; returns without synchronising."""
+        k, pool, lam = self._diverse_args(k, pool, diversity)
+        check(lib().clipgpu_index_search_diverse_device(self.handle, c_void_p(d_queries), int(nq), k, pool, lam,
+                                                        float(logit_scale), float(logit_bias), c_void_p(d_allow or None),
+                                                        c_void_p(d_idx), c_void_p(d_score), c_void_p(d_pool_idx or None),
+                                                        c_void_p(d_pool_score or None), c_void_p(stream or None)))
 
     @staticmethod
     def _range_args(threshold, limit, what: str) -> Tuple[float, int]:

@@ -678,6 +678,42 @@ int clipgpu_index_search_grouped_device(clipgpu_index* ix, const float* d_querie
                                         float logit_scale, float logit_bias, const uint32_t* d_allow, int64_t* d_idx,
                                         float* d_score, int64_t* d_group, void* stream);
 
+/* ---- diversified search: maximal marginal relevance over a pool of the best rows ------------------------------
+ * A library holds bursts, near-identical edits and re-saved copies, and the k best rows of a query are then k
+ * pictures of one scene.  This search takes a POOL of the P best rows and picks k of them one by one, trading a
+ * candidate's relevance against its similarity to what is already picked (MMR), on the device: nothing but the
+ * result comes back (kernels/diverse.hip; DESIGN.md, embedding index, diversified search).
+ * 1. The pool: c[0 .. P), l[0 .. P) is clipgpu_index_search_filtered(queries, k = pool, ...), ids, order, score bits
+ *    and (-1, -inf) padding; removed and filtered rows are never candidates.  1 <= k <= pool <= CLIPGPU_TOPK_MAX.
+ * 2. G[t][u] = fmaf(dot(row c[t], row c[u]), logit_scale, logit_bias) over the rows as stored (a 16-bit index
+ *    widens them exactly): clipgpu_similarity's bits, so relevance and redundancy are in the same logit units.
+ * 3. All in f32, every operation rounded once: lam = diversity, a = 1.0f - lam.  Step 0 takes candidate 0.  m[t]
+ *    starts at -inf; after taking s, m[t] = G[s][t] where G[s][t] > m[t] (a NaN never raises it).  Step j >= 1
+ *    takes the real candidate not yet taken with the best v[t] = a * l[t] - lam * m[t] in the search's order of
+ *    scores (descending, a NaN below -inf), equal v by the lower pool position.  Padding is never taken.
+ * 4. out_idx int64 [nq][k], out_score f32 [nq][k]: the taken candidates in the order taken, each with its own
+ *    search logit l (not v), bit for bit; (-1, -inf) once the real candidates are used up.  out_pool_idx /
+ *    out_pool_score [nq][pool] (both or neither; NULL = not wanted) receive the pool of step 1.
+ * So with finite scores diversity 0 returns the search's first k, k == pool returns a permutation of the pool, and
+ * an index of exact duplicates resolves every tie by pool position.  Exact and bit-reproducible.
+ * Not offered: pools above 128, a diversity per query, diversified forms of the probed, coded and grouped searches.
+ * Work area: a chunk of 256 queries' pool and 256 * pool * pool f32 (16 MiB at pool 128), one device buffer that
+ * the handle allocates at the first such search, grows when a call brings a larger pool (which waits for the
+ * search in flight) and keeps until it is destroyed; a failed allocation is CLIPGPU_ERR_DEVICE and leaves the
+ * index usable.  The _device form: every pointer on the device, ordered on `stream` behind the handle's last
+ * operation on any stream, no synchronisation beyond that of a growing work area.  Mutex, event ordering, chunking
+ * and host staging are those of the other searches.
+ * Refused with CLIPGPU_ERR_INVALID before any launch: a NULL argument; nq <= 0 or an empty index ("Empty batch");
+ * k or pool outside 1 .. CLIPGPU_TOPK_MAX; k > pool; a diversity outside [0, 1] or NaN; one pool output without
+ * the other.  Each message names the limit. */
+int clipgpu_index_search_diverse(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, int64_t pool,
+                                 float diversity, float logit_scale, float logit_bias, const uint32_t* allow,
+                                 int64_t* out_idx, float* out_score, int64_t* out_pool_idx, float* out_pool_score);
+int clipgpu_index_search_diverse_device(clipgpu_index* ix, const float* d_queries, int64_t nq, int64_t k,
+                                        int64_t pool, float diversity, float logit_scale, float logit_bias,
+                                        const uint32_t* d_allow, int64_t* d_idx, float* d_score,
+                                        int64_t* d_pool_idx, float* d_pool_score, void* stream);
+
 /* ---- data-parallel sharding + the RCCL all-gather (north_star: "batches shard
  * data-parallel across the 8 GPUs of one node with an RCCL all-gather over xGMI only for the final
  * embedding matrix").  The reference has no multi-device path: embed_images / embed_texts

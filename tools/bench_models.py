@@ -832,6 +832,90 @@ def topk_grouped_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 16, 256), 
                 print(json.dumps(out), flush=True)
 
 
+def topk_diverse_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 16, 256), pools=(32, 128), centres=1024,
+                     sigma=0.05, lam=0.5):
+    """The diversified search (search_diverse_device) over the clustered f32 gallery of topk_grouped_leg: a query's
+    best rows are near-copies of one another, the case the re-ranking is for.  Per (Q, pool), legs alternating in
+    one process (rotating order; wall-clock milliseconds around a synchronised call after `warmup` rounds, because
+    one leg loops on the host): search_diverse at k; search_diverse at k = 1 (the pool, the whole Gram matrix and
+    one greedy step); search_device at k = pool (stage 1 alone); and the path it replaces -- search_device, a torch
+    gather of the pool's rows, torch.bmm, the copy to the host and the greedy loop in numpy.  The re-ranking's cost
+    is diverse - search; the Gram kernel's share is estimated as diverse(k = 1) - search and the greedy kernel's
+    k - 1 further steps as diverse(k) - diverse(k = 1).  The host path's selection is compared with the device's
+    wherever its Gram matrix (another summation order) has the same bits; the count of equal rows is reported."""
+    from open_clip_inference import EmbeddingIndex
+    torch.manual_seed(0)
+    s = torch.cuda.current_stream().cuda_stream
+    cen0 = torch.nn.functional.normalize(torch.randn(centres, E, device="cuda"), dim=1)
+    j = torch.arange(N, device="cuda")
+    g = torch.nn.functional.normalize(cen0[j // (N // centres)] + sigma * torch.randn(N, E, device="cuda"), dim=1).contiguous()
+
+    def wall_ms(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    with EmbeddingIndex(E, N) as ix:
+        ix.add_device(g.data_ptr(), N, s)
+        for Q in Qs:
+            q = torch.nn.functional.normalize(cen0[torch.randint(0, centres, (Q,), device="cuda")] +
+                                              sigma * torch.randn(Q, E, device="cuda"), dim=1).contiguous()
+            for P in pools:
+                di, ds = torch.empty((Q, k), dtype=torch.int64, device="cuda"), torch.empty((Q, k), device="cuda")
+                pi, ps = torch.empty((Q, P), dtype=torch.int64, device="cuda"), torch.empty((Q, P), device="cuda")
+                host = {}
+
+                def diverse(kk):
+                    ix.search_diverse_device(q.data_ptr(), Q, kk, di.data_ptr(), ds.data_ptr(), lam, P, 100.0, 0.0, s)
+
+                def search():
+                    ix.search_device(q.data_ptr(), Q, P, pi.data_ptr(), ps.data_ptr(), 100.0, 0.0, s)
+
+                def host_path():
+                    search()
+                    rows = g[pi.clamp(min=0)]  # [Q][P][E]
+                    G = (torch.bmm(rows, rows.transpose(1, 2)) * 100.0).cpu().numpy()
+                    c, l = pi.cpu().numpy(), ps.cpu().numpy()
+                    a, lm = np.float32(1.0) - np.float32(lam), np.float32(lam)
+                    out = np.zeros((Q, k), np.int64)
+                    for i in range(Q):
+                        m, open_ = np.full(P, -np.inf, np.float32), np.ones(P, bool)
+                        t = 0
+                        for step in range(k):
+                            if step:
+                                v = np.where(open_, a * l[i] - lm * m, -np.inf)
+                                t = int(np.argmax(v))
+                            out[i, step], open_[t] = c[i, t], False
+                            m = np.maximum(m, G[i, t])
+                    host["idx"] = out
+
+                legs = [("diverse", lambda: diverse(k)), ("diverse_k1", lambda: diverse(1)), ("search_pool", search),
+                        ("host_path", host_path)]
+                ms = {name: [] for name, _ in legs}
+                for rnd in range(warmup + runs):
+                    r = rnd % len(legs)
+                    for name, fn in legs[r:] + legs[:r]:  # every leg follows every other equally often
+                        v = wall_ms(fn)
+                        if rnd >= warmup:
+                            ms[name].append(v)
+                diverse(k)
+                torch.cuda.synchronize()
+                same = int((di.cpu().numpy() == host["idx"]).all(axis=1).sum())
+                out = {"measure": "topk_diverse", "Q": Q, "k": k, "pool": P, "N": N, "E": E, "diversity": lam, "runs": runs,
+                       "clock": "wall, synchronised", "rows_equal_to_host_path": [same, Q]}
+                for name, v in ms.items():
+                    out[name] = _stats(v, N * E * 4)
+                med = {name: out[name]["ms_median"] for name in ms}
+                out["rerank_ms"] = round(med["diverse"] - med["search_pool"], 3)
+                out["gram_ms_est"] = round(med["diverse_k1"] - med["search_pool"], 3)
+                out["greedy_ms_est"] = round(med["diverse"] - med["diverse_k1"], 3)
+                out["diverse_over_search"] = round(med["diverse"] / med["search_pool"], 3)
+                out["diverse_over_host_path"] = round(med["diverse"] / med["host_path"], 3)
+                print(json.dumps(out), flush=True)
+
+
 def topk_routes_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 2, 4, 8, 12, 16)):
     """The measurement kNarrowRows (csrc/kernels/kernels.hpp) is set by: for every query count the
     few-query kernel can take, that kernel (route 2) against the wide one (route 1) on an f32 gallery,
@@ -1066,6 +1150,8 @@ if __name__ == "__main__":
         topk_compound_leg()
     if "topkgrouped" in which:  # the grouped search, collapse on and off, against the plain search and similarity + amax + topk
         topk_grouped_leg()
+    if "topkdiverse" in which:  # the diversified search against its stage-1 search and the gather + bmm + host-loop path
+        topk_diverse_leg()
     if "kmeans" in which:  # one k-means iteration: assign against the range search, the integer-sum update
         kmeans_leg()
     if "ivf" in which:  # the probed search against the plain search on a clustered gallery
