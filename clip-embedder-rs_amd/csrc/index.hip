@@ -68,6 +68,11 @@
 // search for the pool of P candidates into an area of the handle's (or the caller's pool buffers), then
 // launch_diverse, which fills the chunk's Gram matrices [rows][P][P] behind the pool and selects.  The area is
 // lazy, grown when a call brings a larger P, kept until the handle is destroyed.
+//
+// Neighbours of stored rows and the k-NN graph (clipgpu_index_neighbors[_device]; kernels/knn.hip): the query rows
+// are gallery rows, named by id or every slot.  One span cut per call (knn_plan), then as many launches of
+// launch_knn as the search workspace asks for; the device form writes the caller's buffers, the host form stages
+// pieces of 8192 rows in an area of the handle's, lazy and kept like the others.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -160,6 +165,8 @@ struct clipgpu_index {
                                  // [kQueryChunk][kTopkMax]; lazy, kept likewise; NULL = every row ungrouped
   char* dv_work = nullptr;       // the diversified search: what diverse_buffers places, for pools up to dv_work_n;
   int64_t dv_work_n = 0;         // lazy, grown on demand, kept likewise
+  char* kn_work = nullptr;       // neighbours, host form: a piece's ids, indices and scores (KnnWork), kn_work_n rows;
+  int64_t kn_work_n = 0;         // lazy, kept likewise
   hipStream_t stream = nullptr;  // the host-buffer forms' stream
   hipEvent_t done = nullptr;     // recorded after every device-side operation
 };
@@ -1059,9 +1066,90 @@ int diverse_host(clipgpu_index* ix, const SearchReq& r, const DiverseReq& d, int
   });
 }
 
+// ---- neighbours of stored rows and the k-NN graph (kernels/knn.hip) ------------------------------------------
+// ids [n] (device for the device form, host for the host form), or NULL: every slot, n == size, graph semantics.
+struct KnnReq { const int64_t* ids; int64_t n, k; float scale, bias; const uint32_t* allow; };
+constexpr int64_t kKnnPiece = 8192;  // query rows the host form stages at once: 128 panels
+// The host form's area: a piece's ids int64 [kKnnPiece], indices int64 and scores f32 [kKnnPiece][kTopkMax].
+struct KnnWork { int64_t* ids; int64_t* idx; float* score; };
+
+// host: r.ids are host ids, refused here if one is out of range, before any device call.
+std::unique_lock<std::mutex> enter_knn(clipgpu_index* ix, const KnnReq& r, const void* idx, const void* score, bool host) {
+  if (!ix || !idx || !score) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+  if (r.n <= 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");
+  if (r.k < 1 || r.k > CLIPGPU_TOPK_MAX)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "k must be in 1.." + std::to_string(CLIPGPU_TOPK_MAX) +
+                                           " (clipgpu_index_search_deep searches deeper, for a query given as a row)");
+  std::unique_lock<std::mutex> lk(ix->mu);
+  if (ix->size == 0) throw ClipErr(CLIPGPU_ERR_INVALID, "Empty batch");  // an empty gallery
+  if (!r.ids && r.n != ix->size)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "without ids n must be the index's size, " + std::to_string(ix->size) + ", got " +
+                                           std::to_string(r.n));
+  if (host && r.ids) check_ids_in_range(ix, r.ids, r.n);
+  HIP_CHECK(hipSetDevice(ix->device));
+  return lk;
+}
+
+// Query rows [r0, r0 + rows) of a call on `s`, into d_idx / d_score [rows][k]: as many launches as the search
+// workspace asks for at the call's span cut p, in stream order (they share it).  d_ids: the rows' ids, or NULL.
+// The validity bits of a query row: the filter itself for the graph, the live bits alone for named rows.
+void knn_on(clipgpu_index* ix, const KnnReq& r, const TopkPlan& p, const int64_t* d_ids, int64_t r0, int64_t rows,
+            const uint32_t* mask, int64_t* d_idx, float* d_score, hipStream_t s) {
+  const uint32_t* qvalid = !r.ids ? mask : ix->n_dead ? ix->d_live : nullptr;
+  const int64_t step = knn_launch_rows(p, (int)r.k, ix->ws_blocks);
+  for (int64_t q0 = 0; q0 < rows; q0 += step) {
+    const int m = (int)std::min(step, rows - q0);
+    HIP_CHECK(launch_knn({ix->gallery, ix->dtype, (int)ix->size, (int)ix->E, d_ids ? d_ids + q0 : nullptr, r0 + q0, m,
+                          (int)r.k, r.scale, r.bias, p, ix->d_ws, (long)ix->ws_blocks * 64 * kTopkMax, mask, qvalid,
+                          d_idx + q0 * r.k, d_score + q0 * r.k, s}));
+  }
+  mark_last(ix, s);
+}
+
+int knn_device(clipgpu_index* ix, const KnnReq& r, int64_t* d_idx, float* d_score, hipStream_t s) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_knn(ix, r, d_idx, d_score, false);
+    order_after_last(ix, s);
+    const uint32_t* mask = build_mask(ix, r.allow, s);
+    knn_on(ix, r, knn_plan(ix->size, (r.n + 63) / 64, ix->ws_blocks), r.ids, 0, r.n, mask, d_idx, d_score, s);
+  });
+}
+
+int knn_host(clipgpu_index* ix, const KnnReq& r, int64_t* out_idx, float* out_score) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_knn(ix, r, out_idx, out_score, true);
+    HIP_CHECK(hipEventSynchronize(ix->done));  // the filter area and the staging area are free
+    grow(ix->kn_work, ix->kn_work_n, kKnnPiece, (size_t)kKnnPiece * (8 + (size_t)kTopkMax * 12));
+    const KnnWork w = {(int64_t*)ix->kn_work, (int64_t*)(ix->kn_work + kKnnPiece * 8),
+                       (float*)(ix->kn_work + kKnnPiece * 8 + kKnnPiece * kTopkMax * 8)};
+    if (r.allow) HIP_CHECK(copy_h2d(ix->d_eff, r.allow, (size_t)live_words(ix->size) * 4));
+    const uint32_t* mask = build_mask(ix, r.allow ? ix->d_eff : nullptr, ix->stream);
+    const TopkPlan p = knn_plan(ix->size, (r.n + 63) / 64, ix->ws_blocks);
+    for (int64_t r0 = 0; r0 < r.n; r0 += kKnnPiece) {
+      const int64_t rows = std::min(kKnnPiece, r.n - r0);
+      if (r.ids) HIP_CHECK(copy_h2d(w.ids, r.ids + r0, (size_t)rows * 8));
+      knn_on(ix, r, p, r.ids ? w.ids : nullptr, r0, rows, mask, w.idx, w.score, ix->stream);
+      HIP_CHECK(hipStreamSynchronize(ix->stream));
+      HIP_CHECK(copy_d2h(out_idx + r0 * r.k, w.idx, (size_t)rows * r.k * 8));
+      HIP_CHECK(copy_d2h(out_score + r0 * r.k, w.score, (size_t)rows * r.k * 4));
+    }
+  });
+}
+
 }  // namespace
 
 extern "C" {
+
+int clipgpu_index_neighbors(clipgpu_index* ix, const int64_t* ids, int64_t n, int64_t k, float logit_scale,
+                            float logit_bias, const uint32_t* allow, int64_t* out_idx, float* out_score) {
+  return knn_host(ix, {ids, n, k, logit_scale, logit_bias, allow}, out_idx, out_score);
+}
+
+int clipgpu_index_neighbors_device(clipgpu_index* ix, const int64_t* d_ids, int64_t n, int64_t k, float logit_scale,
+                                   float logit_bias, const uint32_t* d_allow, int64_t* d_idx, float* d_score,
+                                   void* stream) {
+  return knn_device(ix, {d_ids, n, k, logit_scale, logit_bias, d_allow}, d_idx, d_score, (hipStream_t)stream);
+}
 
 int clipgpu_index_search_diverse(clipgpu_index* ix, const float* queries, int64_t nq, int64_t k, int64_t pool,
                                  float diversity, float logit_scale, float logit_bias, const uint32_t* allow,
@@ -1490,6 +1578,7 @@ void clipgpu_index_destroy(clipgpu_index* ix) {
   if (ix->cp_work) (void)hipFree(ix->cp_work);
   if (ix->gp_labels) (void)hipFree(ix->gp_labels);
   if (ix->dv_work) (void)hipFree(ix->dv_work);
+  if (ix->kn_work) (void)hipFree(ix->kn_work);
   if (ix->work) (void)hipFree(ix->work);
   if (ix->gallery) (void)hipFree(ix->gallery);
   delete ix;

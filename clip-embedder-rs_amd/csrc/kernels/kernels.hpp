@@ -340,6 +340,38 @@ struct DiverseArgs {
 };
 hipError_t launch_diverse(const DiverseArgs& a);
 
+// Neighbours of stored rows (kernels/knn.hip): launch_topk with the queries taken from the gallery and each
+// query's own row left out.  Query row r (r < nq) is gallery row ids[r] (device int64), or id0 + r when ids is
+// NULL.  Its result, out_idx / out_score [nq][k], is launch_topk's for the query widen(g[row]) over the columns
+// mask allows (NULL: all) other than the row itself, bit for bit, (-1, -inf) beyond the rows there are.  A query
+// row whose id is outside [0, N), or whose bit in qvalid (device words as launch_topk_mask reads them: live bits
+// or the mask itself; NULL = every row valid; given only with a mask) is clear, gets k x (-1, -inf) and reads
+// nothing.  One phase-1 launch over (ceil(nq / 64) panels x plan.n_spans spans) into ws, then launch_topk_merge;
+// ws holds ws_entries >= ceil(nq / 64) * 64 * n_spans * k entries of 8 bytes.  1 <= k <= kTopkMax, E % 16 == 0.
+// knn_plan(N, panels, max_blocks): the span cut for a call of `panels` panels in all with a workspace sized for
+// max_blocks wide blocks -- the search's cut for few panels, one span from 512 panels on, g_topk_span_cols
+// columns when that hook is set; knn_launch_rows: the query rows (a multiple of 64) that workspace then holds
+// per launch at k.
+struct KnnArgs {
+  const void* g;  // [N][E] of dtype (TopkGal)
+  int dtype, N, E;
+  const int64_t* ids;
+  long id0;
+  int nq, k;
+  float scale, bias;
+  TopkPlan plan;
+  void* ws;
+  long ws_entries;
+  const uint32_t* mask;
+  const uint32_t* qvalid;
+  int64_t* out_idx;
+  float* out_score;
+  hipStream_t stream;
+};
+TopkPlan knn_plan(long N, long panels, int max_blocks);
+long knn_launch_rows(const TopkPlan& p, int k, int max_blocks);
+hipError_t launch_knn(const KnnArgs& a);
+
 // Inverted lists (kernels/lists.hip): the CSR of the rows by label.  label: int32 [N], -1 = not in any list,
 // else below C (1 <= C <= kClusterMaxCentroids).  offsets int32 [C + 1]: offsets[c] = the rows with a label
 // below c; ids int32 [offsets[C]]: the rows of list c at [offsets[c], offsets[c + 1]), ascending -- a pure

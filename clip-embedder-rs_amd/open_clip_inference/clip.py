@@ -193,6 +193,17 @@ class Clip:
                                           allow=allow)
         return [[(int(i), float(s)) for i, s in zip(ri, rs) if i >= 0] for ri, rs in zip(idx, score)]
 
+    def similar(self, index, ids, k: int, allow=None) -> List[List[Tuple[int, float]]]:
+        """More like this: per image ``ids[r]`` of ``index`` its k closest other images as (gallery index,
+        cosine), best first (``EmbeddingIndex.neighbors`` at scale 1, bias 0)."""
+        idx, score = index.neighbors(ids, k, allow=allow)
+        return [[(int(i), float(s)) for i, s in zip(ri, rs) if i >= 0] for ri, rs in zip(idx, score)]
+
+    def knn_graph(self, index, k: int, allow=None) -> Tuple[np.ndarray, np.ndarray]:
+        """The k-NN graph of ``index``: (indices int64 [len(index), k], cosines f32), each row's k closest other
+        rows, (-1, -inf) where there are none (``EmbeddingIndex.knn_graph`` at scale 1, bias 0)."""
+        return index.knn_graph(k, allow=allow)
+
     def _search_groups(self, index, groups, k: int, op: str, allow) -> List[List[Tuple[int, float]]]:
         groups = [list(g) for g in groups]
         lims = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int64)

@@ -62,7 +62,8 @@ class EmbeddingIndex:
     ``search`` for k up to 4096, as exact.  ``search_compound`` takes queries made of up to 16 terms and scores a
     row by the smallest (all-of) or largest (any-of) of its term logits, in one scan.  ``set_groups`` labels rows
     and ``search_grouped`` returns the k best groups, each by its best row.  ``search_diverse`` re-ranks a pool of
-    the best rows for variety (maximal marginal relevance), on the device.  ``range_search``
+    the best rows for variety (maximal marginal relevance), on the device.  ``neighbors`` returns the k rows
+    closest to stored rows and ``knn_graph`` does so for every row, the row itself left out.  ``range_search``
     returns every row at or above a score threshold instead of the k best, and ``duplicates`` joins the
     gallery against itself at a threshold; neither builds the score matrix.  ``assign`` gives every row its
     nearest of C centroids and ``kmeans`` puts the rows into groups, reproducibly.  ``partition`` cuts the
@@ -435,6 +436,46 @@ class EmbeddingIndex:
                                                         float(logit_scale), float(logit_bias), c_void_p(d_allow or None),
                                                         c_void_p(d_idx), c_void_p(d_score), c_void_p(d_pool_idx or None),
                                                         c_void_p(d_pool_score or None), c_void_p(stream or None)))
+
+    # ---- neighbours of stored rows and the k-NN graph ------------------------------------------------------
+    def _neighbors(self, ids, n: int, k, logit_scale, logit_bias, allow) -> Tuple[np.ndarray, np.ndarray]:
+        k = self._grouped_k(k)
+        words = self._allow_words(allow)
+        idx = np.empty((n, k), np.int64)
+        score = np.empty((n, k), np.float32)
+        check(lib().clipgpu_index_neighbors(self.handle, None if ids is None else ids.ctypes.data, n, k,
+                                            float(logit_scale), float(logit_bias),
+                                            None if words is None else words.ctypes.data, idx.ctypes.data,
+                                            score.ctypes.data))
+        return idx, score
+
+    def neighbors(self, ids, k: int, logit_scale: float = 1.0, logit_bias: float = 0.0, allow=None
+                  ) -> Tuple[np.ndarray, np.ndarray]:
+        """The k rows closest to each stored row ``ids[r]`` ("more like this"): (indices int64 [n, k], scores f32
+        [n, k]), the k best live allowed rows other than the row itself, in ``search``'s order with ``search``'s
+        score bits -- exactly ``search(rows_at([i]), k, ..., allow=allow & ~{i})``, without the rows leaving the
+        device.  The row is left out before the selection, so exact duplicates of it are all kept (dropping the
+        first hit of ``search(k + 1)`` loses one of them or keeps the row).  ``allow`` filters the candidates only;
+        a removed row gets (-1, -inf) throughout, as do the slots beyond the rows there are.  ``ids`` may repeat, in
+        any order; one outside [0, len(self)) raises.  1 <= k <= 128."""
+        x = self._ids(ids)
+        return self._neighbors(x, x.size, k, logit_scale, logit_bias, allow)
+
+    def knn_graph(self, k: int, logit_scale: float = 1.0, logit_bias: float = 0.0, allow=None
+                  ) -> Tuple[np.ndarray, np.ndarray]:
+        """The k-NN graph of the gallery: ``neighbors(arange(len(self)), k, ...)`` in one pass, as (indices int64
+        [len(self), k], scores), except that the graph is over the live allowed rows: a row that is removed or
+        not allowed gets (-1, -inf) throughout and costs no work."""
+        return self._neighbors(None, len(self), k, logit_scale, logit_bias, allow)
+
+    def neighbors_device(self, d_ids: int, n: int, k: int, d_idx: int, d_score: int, logit_scale: float = 1.0,
+                         logit_bias: float = 0.0, stream: int = 0, d_allow: int = 0) -> None:
+        """``neighbors`` on device pointers (ids int64 [n] in, 0 = every slot with ``knn_graph``'s rule and n =
+        len(self); int64 [n, k] and f32 [n, k] out), ordered on ``stream``; returns without synchronising.  An id
+        outside [0, len(self)) gives its row (-1, -inf) throughout."""
+        check(lib().clipgpu_index_neighbors_device(self.handle, c_void_p(d_ids or None), int(n), self._grouped_k(k),
+                                                   float(logit_scale), float(logit_bias), c_void_p(d_allow or None),
+                                                   c_void_p(d_idx), c_void_p(d_score), c_void_p(stream or None)))
 
     @staticmethod
     def _range_args(threshold, limit, what: str) -> Tuple[float, int]:

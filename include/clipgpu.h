@@ -714,6 +714,37 @@ int clipgpu_index_search_diverse_device(clipgpu_index* ix, const float* d_querie
                                         const uint32_t* d_allow, int64_t* d_idx, float* d_score,
                                         int64_t* d_pool_idx, float* d_pool_score, void* stream);
 
+/* ---- neighbours of stored rows and the k-NN graph --------------------------------------------------------------
+ * "Which rows are closest to this stored row": a more-like-this button, near-duplicate grouping without a fixed
+ * threshold, label propagation, reciprocal re-ranking; for every row at once, the k-NN graph of the gallery.  The
+ * query rows are gallery rows named by id and never leave the device: no f32 copy of them exists, a 16-bit index
+ * is read as 16 bits (kernels/knn.hip; DESIGN.md, embedding index, neighbours).
+ * 1. For i = ids[r], row r of out_idx int64 [n][k] / out_score f32 [n][k] holds the k best live allowed rows
+ *    j != i by fmaf(dot(row i, row j), logit_scale, logit_bias) over the rows as stored: clipgpu_similarity's bits
+ *    of the index's rows against themselves, in the search's order (descending, equal scores by ascending row),
+ *    (-1, -inf) beyond the rows there are.  Bit for bit it is clipgpu_index_search_filtered(the row that
+ *    clipgpu_index_get_rows_at gives for i, k, ..., allow with bit i cleared).  The row itself is left out before
+ *    the selection, so a row with k or more exact duplicates below its own id still gets k of them.
+ * 2. allow filters the candidates only: a live row that is not allowed still gets its neighbours among the allowed
+ *    rows.  A removed row gets k x (-1, -inf).  ids may repeat and need not be sorted.  1 <= k <= CLIPGPU_TOPK_MAX.
+ * 3. ids == NULL is the k-NN graph: n must be clipgpu_index_size(ix), row r is slot r, and a slot that is removed
+ *    OR not allowed gets k x (-1, -inf) and costs no work: the graph is over the allowed live rows.
+ * Exact and bit-reproducible; the scores of (i, j) and (j, i) carry the same bits.
+ * Not offered: k above 128; neighbours through the probed, coded or grouped searches; a join between two indexes;
+ * the symmetric form that computes each pair once.
+ * The host form refuses an id outside [0, size) with CLIPGPU_ERR_INVALID before any device call, and stages pieces
+ * of 8192 rows in a 12 MiB device buffer that the handle allocates at the first such call and keeps.  The _device
+ * form: every pointer on the device, ordered on `stream` behind the handle's last operation on any stream; it does
+ * not synchronise and reads nothing back, so an id outside [0, size) there yields k x (-1, -inf) for its row and
+ * reads nothing out of bounds.  Mutex and event ordering are those of the other searches.
+ * Refused with CLIPGPU_ERR_INVALID before any launch: a NULL output; n <= 0 or an empty index ("Empty batch"); k
+ * outside 1 .. CLIPGPU_TOPK_MAX; ids == NULL with n != size. */
+int clipgpu_index_neighbors(clipgpu_index* ix, const int64_t* ids, int64_t n, int64_t k, float logit_scale,
+                            float logit_bias, const uint32_t* allow, int64_t* out_idx, float* out_score);
+int clipgpu_index_neighbors_device(clipgpu_index* ix, const int64_t* d_ids, int64_t n, int64_t k, float logit_scale,
+                                   float logit_bias, const uint32_t* d_allow, int64_t* d_idx, float* d_score,
+                                   void* stream);
+
 /* ---- data-parallel sharding + the RCCL all-gather (north_star: "batches shard
  * data-parallel across the 8 GPUs of one node with an RCCL all-gather over xGMI only for the final
  * embedding matrix").  The reference has no multi-device path: embed_images / embed_texts

@@ -916,6 +916,94 @@ def topk_diverse_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 16, 256), 
                 print(json.dumps(out), flush=True)
 
 
+def topk_knn_leg(E=512, k=10, runs=7, warmup=2, centres=4096, sigma=0.05, matrix_runs=3):
+    """Neighbours of stored rows (neighbors_device) over the clustered gallery of topk_grouped_leg: the k-NN graph
+    of 2^17 rows (f32 and f16 storage) and the neighbours of 1, 16 and 256 ids over 2^20 rows (f32).  Per cell,
+    legs alternating in one process (rotating order), medians of `runs` device-event timings after `warmup`
+    rounds: the new call; what there was before it -- a device gather of the rows as f32 (torch indexing of the
+    widened gallery, which spares a 16-bit index's widening) and search_device at k + 1 in chunks of 256, the
+    host pass that drops the row itself not timed; and the matrix path, the same gather, clipgpu_similarity_device
+    and torch.topk(k + 1) per chunk.  The matrix path of the graph takes seconds per round, so it is timed
+    `matrix_runs` times after one warm-up round.  For the f32 graph `duplicates` at the threshold that the median
+    k-th neighbour score sets (about k pairs per row) is timed once on the wall clock, for scale: it is a host
+    form with a host sort, not a baseline.  The new call's rows are compared with the search route's with the row
+    itself dropped (where the row is among its own k + 1 results); the count of equal rows is reported."""
+    import ctypes
+    from open_clip_inference import EmbeddingIndex
+    torch.manual_seed(0)
+    L = _lib.lib()
+    s = torch.cuda.current_stream().cuda_stream
+    cells = [("graph", 1 << 17, None, "f32"), ("graph", 1 << 17, None, "f16")] + [("ids", 1 << 20, n, "f32") for n in (1, 16, 256)]
+    made = {}
+    for what, N, n_ids, dt in cells:
+        if N not in made:
+            made.clear()
+            cen0 = torch.nn.functional.normalize(torch.randn(centres, E, device="cuda"), dim=1)
+            j = torch.arange(N, device="cuda")
+            made[N] = torch.nn.functional.normalize(cen0[j // (N // centres)] + sigma * torch.randn(N, E, device="cuda"),
+                                                    dim=1).contiguous()
+        g = made[N]
+        esz, tdt = INDEX_DTYPES[dt]
+        gw = g if tdt is None else g.to(tdt).float()
+        ids = torch.arange(N, device="cuda") if n_ids is None else torch.randint(0, N, (n_ids,), device="cuda")
+        n = len(ids)
+        with EmbeddingIndex(E, N, dtype=dt) as ix:
+            ix.add_device(g.data_ptr(), N, s)
+            di, ds = torch.empty((n, k), dtype=torch.int64, device="cuda"), torch.empty((n, k), device="cuda")
+            bi, bs = torch.empty((n, k + 1), dtype=torch.int64, device="cuda"), torch.empty((n, k + 1), device="cuda")
+            mat = torch.empty(min(n, 256), N, device="cuda")
+
+            def new():
+                ix.neighbors_device(0 if n_ids is None else ids.data_ptr(), n, k, di.data_ptr(), ds.data_ptr(), 1.0, 0.0, s)
+
+            def search_route():
+                for c0 in range(0, n, 256):
+                    rows = gw[ids[c0:c0 + 256]]
+                    ix.search_device(rows.data_ptr(), len(rows), k + 1, bi[c0:].data_ptr(), bs[c0:].data_ptr(), 1.0, 0.0, s)
+
+            def matrix_route():
+                for c0 in range(0, n, 256):
+                    rows = gw[ids[c0:c0 + 256]]
+                    _lib.check(L.clipgpu_similarity_device(ctypes.c_void_p(rows.data_ptr()), len(rows),
+                                                           ctypes.c_void_p(gw.data_ptr()), N, E, 1.0, 0.0, 2, 1,
+                                                           ctypes.c_void_p(mat.data_ptr()), ctypes.c_void_p(s)))
+                    torch.topk(mat[:len(rows)], k + 1, dim=1)
+
+            legs = [("neighbors", new), ("gather_search_k1", search_route)]
+            ms = {name: [] for name, _ in legs}
+            for rnd in range(warmup + runs):
+                r = rnd % len(legs)
+                for name, fn in legs[r:] + legs[:r]:
+                    t = _event_ms(fn)
+                    if rnd >= warmup:
+                        ms[name].append(t)
+            slow = what == "graph"
+            ms["gather_matrix_topk"] = [_event_ms(matrix_route) for _ in range((1 + matrix_runs) if slow else warmup + runs)][
+                1 if slow else warmup:]
+            torch.cuda.synchronize()
+            a_i, b_i, own = di.cpu().numpy(), bi.cpu().numpy(), ids.cpu().numpy()[:, None]
+            has_self = (b_i == own).any(axis=1)
+            dropped = np.stack([r[r != o][:k] for r, o in zip(b_i, own[:, 0])])
+            same = int(((a_i == dropped).all(axis=1) & has_self).sum())
+            out = {"measure": "topk_knn", "what": what, "dtype": dt, "N": N, "E": E, "k": k, "ids": n, "runs": runs,
+                   "matrix_runs": len(ms["gather_matrix_topk"]), "rows_equal_to_search_route": [same, int(has_self.sum())]}
+            for name, v in ms.items():
+                out[name] = _stats(v, N * E * esz)
+            med = {name: out[name]["ms_median"] for name in ms}
+            out["neighbors_over_search_route"] = round(med["neighbors"] / med["gather_search_k1"], 3)
+            out["neighbors_over_matrix_route"] = round(med["neighbors"] / med["gather_matrix_topk"], 3)
+            if slow:
+                out["tflops_f32"] = round(2.0 * n * N * E / (med["neighbors"] * 1e-3) / 1e12, 1)
+            if slow and dt == "f32":
+                thr = float(ds[:, k - 1].median())
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                pairs, _ = ix.duplicates(thr, max_pairs=N * k * 4)
+                out["duplicates_wall_ms_once"] = round((time.perf_counter() - t0) * 1e3, 1)
+                out["duplicates_pairs_per_row"] = round(2 * len(pairs) / N, 2)  # a pair is a neighbour of both rows
+            print(json.dumps(out), flush=True)
+
+
 def topk_routes_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 2, 4, 8, 12, 16)):
     """The measurement kNarrowRows (csrc/kernels/kernels.hpp) is set by: for every query count the
     few-query kernel can take, that kernel (route 2) against the wide one (route 1) on an f32 gallery,
@@ -1152,6 +1240,8 @@ if __name__ == "__main__":
         topk_grouped_leg()
     if "topkdiverse" in which:  # the diversified search against its stage-1 search and the gather + bmm + host-loop path
         topk_diverse_leg()
+    if "topkknn" in which:  # neighbours of stored rows and the k-NN graph against gather + search(k + 1) and the matrix path
+        topk_knn_leg()
     if "kmeans" in which:  # one k-means iteration: assign against the range search, the integer-sum update
         kmeans_leg()
     if "ivf" in which:  # the probed search against the plain search on a clustered gallery
