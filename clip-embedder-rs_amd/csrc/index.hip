@@ -73,6 +73,13 @@
 // are gallery rows, named by id or every slot.  One span cut per call (knn_plan), then as many launches of
 // launch_knn as the search workspace asks for; the device form writes the caller's buffers, the host form stages
 // pieces of 8192 rows in an area of the handle's, lazy and kept like the others.
+//
+// Duplicate groups (clipgpu_index_components[_device]; kernels/components.hip): the connected components of the
+// self-join's threshold graph.  One launch_components per call -- init, join-and-hook, flatten -- on one stream
+// under the search's mask, with no chunk loop and nothing read back in between.  The union-find's parent array
+// (int32 per slot of the capacity) and, behind it, the host form's staged labels and the counter are one buffer of
+// the handle's, allocated at the first call and kept until the handle is destroyed.  to_groups has the flatten
+// write the group labels as well (allocated as set_groups allocates them).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -167,6 +174,8 @@ struct clipgpu_index {
   int64_t dv_work_n = 0;         // lazy, grown on demand, kept likewise
   char* kn_work = nullptr;       // neighbours, host form: a piece's ids, indices and scores (KnnWork), kn_work_n rows;
   int64_t kn_work_n = 0;         // lazy, kept likewise
+  char* cc_work = nullptr;       // duplicate groups: parent int32 [capacity], the host form's labels int32 [capacity]
+                                 // and the counter (CcBuf); lazy, kept likewise
   hipStream_t stream = nullptr;  // the host-buffer forms' stream
   hipEvent_t done = nullptr;     // recorded after every device-side operation
 };
@@ -1136,9 +1145,88 @@ int knn_host(clipgpu_index* ix, const KnnReq& r, int64_t* out_idx, float* out_sc
   });
 }
 
+// ---- duplicate groups (kernels/components.hip) ----------------------------------------------------------------
+struct CcReq { float thr, scale, bias; const uint32_t* allow; bool to_groups; };
+// The regions of cc_work.
+struct CcBuf { int32_t* parent; int32_t* label; uint32_t* count; };
+
+// The refusals that need no lock and no device; then the lock and the handle's device.  An empty index is no error.
+std::unique_lock<std::mutex> enter_components(clipgpu_index* ix, bool null_arg, const CcReq& r) {
+  if (!ix || null_arg) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+  if (r.thr != r.thr) throw ClipErr(CLIPGPU_ERR_INVALID, "threshold must not be NaN");
+  std::unique_lock<std::mutex> lk(ix->mu);
+  HIP_CHECK(hipSetDevice(ix->device));
+  return lk;
+}
+
+// Allocated at the first call; a failed allocation is CLIPGPU_ERR_DEVICE and leaves the handle without the
+// buffer, usable.  Callers hold the mutex.
+CcBuf components_buffers(clipgpu_index* ix) {
+  const size_t slots = align256((size_t)ix->capacity * 4);
+  if (!ix->cc_work) HIP_CHECK(hipMalloc((void**)&ix->cc_work, 2 * slots + 256));
+  size_t off = 0;
+  CcBuf b;
+  b.parent = carve<int32_t>(ix->cc_work, off, slots);
+  b.label = carve<int32_t>(ix->cc_work, off, slots);
+  b.count = carve<uint32_t>(ix->cc_work, off, 4);
+  return b;
+}
+
+// The three launches on `s` (ordered behind the handle's last operation by the caller) into device buffers.
+void components_on(clipgpu_index* ix, const CcReq& r, const CcBuf& b, const uint32_t* mask, uint32_t* groups,
+                   int32_t* d_label, uint32_t* d_count, hipStream_t s) {
+  HIP_CHECK(launch_components({ix->gallery, ix->dtype, (int)ix->size, (int)ix->E, r.scale, r.bias, r.thr, mask, b.parent,
+                               d_label, groups, d_count, s}));
+  mark_last(ix, s);
+}
+
+int components_device(clipgpu_index* ix, const CcReq& r, int32_t* d_label, uint32_t* d_count, hipStream_t s) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_components(ix, !d_label && !r.to_groups, r);
+    const CcBuf b = ix->size > 0 ? components_buffers(ix) : CcBuf{};  // an empty index: the count is zeroed, no more
+    uint32_t* groups = r.to_groups && ix->size > 0 ? group_labels(ix) : nullptr;
+    order_after_last(ix, s);
+    const uint32_t* mask = ix->size > 0 ? build_mask(ix, r.allow, s) : nullptr;
+    components_on(ix, r, b, mask, groups, d_label, d_count, s);
+  });
+}
+
+int components_host(clipgpu_index* ix, const CcReq& r, int64_t* out_label, int64_t* out_count) {
+  return guarded([&]() {
+    const std::unique_lock<std::mutex> lk = enter_components(ix, !out_label || !out_count, r);
+    *out_count = 0;
+    if (ix->size == 0) return;
+    HIP_CHECK(hipEventSynchronize(ix->done));  // the filter area and the staged labels are free
+    const CcBuf b = components_buffers(ix);
+    uint32_t* groups = r.to_groups ? group_labels(ix) : nullptr;
+    if (r.allow) HIP_CHECK(copy_h2d(ix->d_eff, r.allow, (size_t)live_words(ix->size) * 4));
+    const uint32_t* mask = build_mask(ix, r.allow ? ix->d_eff : nullptr, ix->stream);
+    components_on(ix, r, b, mask, groups, b.label, b.count, ix->stream);
+    HIP_CHECK(hipStreamSynchronize(ix->stream));
+    std::vector<int32_t> l((size_t)ix->size);
+    uint32_t count = 0;
+    HIP_CHECK(copy_d2h(l.data(), b.label, l.size() * 4));
+    HIP_CHECK(copy_d2h(&count, b.count, 4));
+    for (size_t i = 0; i < l.size(); ++i) out_label[i] = l[i];
+    *out_count = count;
+  });
+}
+
 }  // namespace
 
 extern "C" {
+
+int clipgpu_index_components(clipgpu_index* ix, float threshold, float logit_scale, float logit_bias,
+                             const uint32_t* allow, int to_groups, int64_t* out_label, int64_t* out_count) {
+  return components_host(ix, {threshold, logit_scale, logit_bias, allow, to_groups != 0}, out_label, out_count);
+}
+
+int clipgpu_index_components_device(clipgpu_index* ix, float threshold, float logit_scale, float logit_bias,
+                                    const uint32_t* d_allow, int to_groups, int32_t* d_label, uint32_t* d_count,
+                                    void* stream) {
+  return components_device(ix, {threshold, logit_scale, logit_bias, d_allow, to_groups != 0}, d_label, d_count,
+                           (hipStream_t)stream);
+}
 
 int clipgpu_index_neighbors(clipgpu_index* ix, const int64_t* ids, int64_t n, int64_t k, float logit_scale,
                             float logit_bias, const uint32_t* allow, int64_t* out_idx, float* out_score) {
@@ -1579,6 +1667,7 @@ void clipgpu_index_destroy(clipgpu_index* ix) {
   if (ix->gp_labels) (void)hipFree(ix->gp_labels);
   if (ix->dv_work) (void)hipFree(ix->dv_work);
   if (ix->kn_work) (void)hipFree(ix->kn_work);
+  if (ix->cc_work) (void)hipFree(ix->cc_work);
   if (ix->work) (void)hipFree(ix->work);
   if (ix->gallery) (void)hipFree(ix->gallery);
   delete ix;

@@ -372,6 +372,27 @@ TopkPlan knn_plan(long N, long panels, int max_blocks);
 long knn_launch_rows(const TopkPlan& p, int k, int max_blocks);
 hipError_t launch_knn(const KnnArgs& a);
 
+// Duplicate groups (kernels/components.hip): the connected components of the graph over the rows mask allows
+// (NULL: all) with an edge i-j wherever fmaf(dot(g[i], g[j]), scale, bias) >= threshold, launch_range's join bits
+// and comparison.  label int32 [N] (NULL = not wanted): the smallest row id of the row's component, -1 for a row
+// the mask excludes.  groups (NULL = not wanted): launch_grouped's labels for slots [0, N), the component's label
+// or 0x80000000 | slot for an excluded row.  count (NULL = not wanted): the components, singletons included.
+// parent: work area, int32 [N].  Three launches on the stream (init, join-and-hook over the upper triangle,
+// flatten), nothing read back; N == 0 only zeroes the count.  label or groups must be given; E % 16 == 0.  The cut
+// of the triangle honours g_topk_span_cols.
+struct ComponentsArgs {
+  const void* g;  // [N][E] of dtype (TopkGal)
+  int dtype, N, E;
+  float scale, bias, threshold;
+  const uint32_t* mask;
+  int32_t* parent;
+  int32_t* label;
+  uint32_t* groups;
+  uint32_t* count;
+  hipStream_t stream;
+};
+hipError_t launch_components(const ComponentsArgs& a);
+
 // Inverted lists (kernels/lists.hip): the CSR of the rows by label.  label: int32 [N], -1 = not in any list,
 // else below C (1 <= C <= kClusterMaxCentroids).  offsets int32 [C + 1]: offsets[c] = the rows with a label
 // below c; ids int32 [offsets[C]]: the rows of list c at [offsets[c], offsets[c + 1]), ascending -- a pure

@@ -247,6 +247,18 @@ class Clip:
         pairs, score = index.duplicates(min_cosine, 1.0, 0.0, allow=allow, max_pairs=max_pairs)
         return [(int(i), int(j), float(s)) for (i, j), s in zip(pairs, score)]
 
+    def group_duplicates(self, index, min_cosine: float, allow=None, apply: bool = False) -> List[List[int]]:
+        """Near-duplicates in a gallery as groups: the rows connected by the pairs of ``find_duplicates(index,
+        min_cosine, allow)``, without the pair list.  Returns the groups of two or more rows, each ascending,
+        ordered by their first row.  ``apply=True`` also makes the groups the index's group labels (every other row
+        ungrouped), after which ``search_grouped`` returns one image per duplicate group
+        (``EmbeddingIndex.duplicate_groups``)."""
+        labels, _ = index.duplicate_groups(min_cosine, 1.0, 0.0, allow=allow, set_groups=apply)
+        ids = np.flatnonzero(labels >= 0)
+        ids = ids[np.argsort(labels[ids], kind="stable")]  # by label, the smallest row of the group, then by row
+        groups = np.split(ids, np.flatnonzero(np.diff(labels[ids])) + 1) if ids.size else []
+        return [[int(i) for i in g] for g in groups if len(g) >= 2]
+
     def cluster(self, index, n_clusters: int, seed: int = 0, max_iter: int = 25, allow=None
                 ) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """Puts the live (and allowed) rows of ``index`` into ``n_clusters`` groups by cosine (spherical

@@ -65,7 +65,9 @@ class EmbeddingIndex:
     the best rows for variety (maximal marginal relevance), on the device.  ``neighbors`` returns the k rows
     closest to stored rows and ``knn_graph`` does so for every row, the row itself left out.  ``range_search``
     returns every row at or above a score threshold instead of the k best, and ``duplicates`` joins the
-    gallery against itself at a threshold; neither builds the score matrix.  ``assign`` gives every row its
+    gallery against itself at a threshold; neither builds the score matrix.  ``duplicate_groups`` gives every row
+    the label of its group of near-duplicates (the connected components of ``duplicates``' pairs) without the pair
+    list.  ``assign`` gives every row its
     nearest of C centroids and ``kmeans`` puts the rows into groups, reproducibly.  ``partition`` cuts the
     gallery into inverted lists by nearest centroid and ``search_probed`` searches only the ``nprobe`` lists
     closest to each query: approximate in which rows it looks at, exact in what it returns for them.
@@ -553,6 +555,43 @@ class EmbeddingIndex:
         self._check_range(rc, total.value, cap, "max_pairs")
         n = total.value
         return np.stack([oi[:n], oj[:n]], axis=1), score[:n].copy()
+
+    def duplicate_groups(self, threshold: float, logit_scale: float = 1.0, logit_bias: float = 0.0, allow=None,
+                         set_groups: bool = False) -> Tuple[np.ndarray, int]:
+        """The near-duplicates as groups instead of pairs: the connected components of the graph whose vertices
+        are the live (and allowed) rows and whose edges are exactly the pairs ``duplicates(threshold, ...)`` lists,
+        computed on the device without the pair list (which is quadratic in the size of a cluster and may exceed
+        any ``max_pairs``).  Returns (labels int64 [len(self)], n_groups int): ``labels[i]`` is the smallest row id
+        of i's component -- a row with no duplicate is its own label -- and -1 for a row that is dead or not
+        allowed; ``n_groups`` counts the components, singletons included.  The result is a function of the rows,
+        the threshold and the filter alone.  ``set_groups=True`` also makes the labels the group labels, on the
+        device: every slot's label is overwritten (a dead or not allowed row becomes ungrouped), after which
+        ``search_grouped`` returns one row per duplicate group.  The first call allocates 8 bytes per slot of
+        the capacity."""
+        thr = float(threshold)
+        if thr != thr:
+            raise ValueError("threshold must not be NaN")
+        words = self._allow_words(allow)
+        labels = np.empty(len(self), np.int64)
+        count = ctypes.c_int64(0)
+        check(lib().clipgpu_index_components(self.handle, thr, float(logit_scale), float(logit_bias),
+                                             None if words is None else words.ctypes.data, int(bool(set_groups)),
+                                             labels.ctypes.data, ctypes.addressof(count)))
+        return labels, int(count.value)
+
+    def duplicate_groups_device(self, threshold: float, d_label: int, d_count: int = 0, logit_scale: float = 1.0,
+                                logit_bias: float = 0.0, stream: int = 0, d_allow: int = 0, set_groups: bool = False
+                                ) -> None:
+        """``duplicate_groups`` on device pointers (labels int32 [len(self)] out, 0 = not wanted, allowed only with
+        ``set_groups``; ``d_count`` uint32 out or 0 = not wanted), ordered on ``stream``; enqueues three launches
+        and returns without synchronising."""
+        thr = float(threshold)
+        if thr != thr:
+            raise ValueError("threshold must not be NaN")
+        check(lib().clipgpu_index_components_device(self.handle, thr, float(logit_scale), float(logit_bias),
+                                                    c_void_p(d_allow or None), int(bool(set_groups)),
+                                                    c_void_p(d_label or None), c_void_p(d_count or None),
+                                                    c_void_p(stream or None)))
 
     def rows_at(self, ids) -> np.ndarray:
         """The rows at ``ids`` as stored, widened to f32 [n, E], in the order of ``ids``; dead rows and

@@ -745,6 +745,36 @@ int clipgpu_index_neighbors_device(clipgpu_index* ix, const int64_t* d_ids, int6
                                    float logit_bias, const uint32_t* d_allow, int64_t* d_idx, float* d_score,
                                    void* stream);
 
+/* ---- duplicate groups: the connected components of the threshold graph ------------------------------------------
+ * "Which rows are the same picture": clipgpu_index_self_join lists the near-duplicate PAIRS, which is quadratic in
+ * the size of a cluster (30 000 re-saves of one picture are 4.5e8 pairs, more than any max_pairs); this gives one
+ * label per row instead, O(size), computed on the device without a pair list (kernels/components.hip; DESIGN.md,
+ * embedding index, duplicate groups).
+ * 1. The graph has the live allowed rows as vertices and an edge i-j wherever score(i, j) >= threshold, with exactly
+ *    the scores and the f32 comparison of clipgpu_index_self_join (a NaN score is no edge, not even at -inf).
+ * 2. out_label int64 [size]: the smallest row id of the row's connected component -- a row without a duplicate is
+ *    its own label -- and -1 for a row that is removed or not allowed.  *out_count: the components, singletons
+ *    included.  The labels are a function of the rows, the threshold and the filter alone: bit-reproducible.
+ * 3. to_groups != 0 also writes the labels into the group labels of clipgpu_index_set_groups, on the device: the
+ *    component's label for a live allowed row, "no group" for every other slot -- EVERY slot's label is
+ *    overwritten -- after which clipgpu_index_search_grouped returns one row per duplicate group.  The group labels
+ *    are allocated as clipgpu_index_set_groups allocates them.
+ * An empty index is no error: no label is written and the count is 0.
+ * Work area: 8 bytes per slot of the capacity (the union-find's parent array and the host form's staged labels),
+ * one device buffer that the handle allocates at the first such call and keeps until it is destroyed; a failed
+ * allocation is CLIPGPU_ERR_DEVICE and leaves the index usable.
+ * The _device form: d_allow, d_label (int32 [size]; may be NULL if to_groups) and d_count (uint32, or NULL) on the
+ * device; three launches ordered on `stream` behind the handle's last operation on any stream, no synchronisation
+ * and nothing read back.  Mutex and event ordering are those of the searches.
+ * Refused with CLIPGPU_ERR_INVALID before any launch: a NaN threshold; a NULL output (the _device form: d_label
+ * NULL without to_groups).
+ * Not offered: approximate grouping through the k-NN graph or the inverted lists; components across two indexes. */
+int clipgpu_index_components(clipgpu_index* ix, float threshold, float logit_scale, float logit_bias,
+                             const uint32_t* allow, int to_groups, int64_t* out_label, int64_t* out_count);
+int clipgpu_index_components_device(clipgpu_index* ix, float threshold, float logit_scale, float logit_bias,
+                                    const uint32_t* d_allow, int to_groups, int32_t* d_label, uint32_t* d_count,
+                                    void* stream);
+
 /* ---- data-parallel sharding + the RCCL all-gather (north_star: "batches shard
  * data-parallel across the 8 GPUs of one node with an RCCL all-gather over xGMI only for the final
  * embedding matrix").  The reference has no multi-device path: embed_images / embed_texts

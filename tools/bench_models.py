@@ -1004,6 +1004,69 @@ def topk_knn_leg(E=512, k=10, runs=7, warmup=2, centres=4096, sigma=0.05, matrix
             print(json.dumps(out), flush=True)
 
 
+def topk_components_leg(N=100_000, E=512, thr=0.99, runs=7, warmup=2, copies=1000, cluster=30_000):
+    """Duplicate groups (duplicate_groups: the connected components of the threshold graph, on the device) against
+    the pair list it replaces (duplicates: the self-join in chunks, its records copied back and sorted on the
+    host), on two galleries of N random unit rows at a cosine of `thr`.  "planted": `copies` rows are exact copies
+    of other rows (about 1 %).  "cluster": `cluster` rows are one row -- cluster^2 / 2 pairs, more than the pair
+    list can hold at any max_pairs, and the worst case for contention in the union-find; there `duplicates` is
+    called once, to record that it overflows and with how many pairs.  Per gallery the legs alternate in one
+    process in rotating order: medians of `runs` timings after `warmup` rounds.  duplicate_groups_device is timed
+    with device events; the two host forms with the host clock (both end in a synchronise and a copy back)."""
+    from open_clip_inference import EmbeddingIndex
+    from open_clip_inference.error import ResultOverflow
+    from open_clip_inference.index import RANGE_MAX
+    torch.manual_seed(0)
+    s = torch.cuda.current_stream().cuda_stream
+
+    def wall_ms(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        return (time.perf_counter() - t0) * 1e3
+
+    for what in ("planted", "cluster"):
+        g = torch.nn.functional.normalize(torch.randn(N, E, device="cuda"), dim=1)
+        n_dup = copies if what == "planted" else cluster
+        dst = torch.randperm(N, device="cuda")[:n_dup]
+        g[dst] = g[torch.randint(0, N, (n_dup,), device="cuda")] if what == "planted" else g[dst[:1]]
+        g = g.contiguous()
+        with EmbeddingIndex(E, N) as ix:
+            ix.add_device(g.data_ptr(), N, s)
+            dl = torch.empty(N, dtype=torch.int32, device="cuda")
+            dc = torch.zeros(1, dtype=torch.int32, device="cuda")
+            legs = [("duplicate_groups_device", lambda: _event_ms(
+                        lambda: ix.duplicate_groups_device(thr, dl.data_ptr(), dc.data_ptr(), stream=s))),
+                    ("duplicate_groups", lambda: wall_ms(lambda: ix.duplicate_groups(thr)))]
+            out = {"measure": "topk_components", "what": what, "N": N, "E": E, "threshold": thr, "runs": runs}
+            if what == "planted":
+                legs.append(("duplicates", lambda: wall_ms(lambda: ix.duplicates(thr))))
+            else:
+                try:
+                    ix.duplicates(thr)
+                    out["duplicates"] = "returned"
+                except ResultOverflow as e:
+                    out["duplicates"] = {"overflow_pairs": int(e.needed), "RANGE_MAX": RANGE_MAX}
+            ms = {name: [] for name, _ in legs}
+            for rnd in range(warmup + runs):
+                r = rnd % len(legs)
+                for name, fn in legs[r:] + legs[:r]:
+                    t = fn()
+                    if rnd >= warmup:
+                        ms[name].append(t)
+            labels, n_groups = ix.duplicate_groups(thr)
+            out["n_groups"], out["rows_in_groups_of_2_or_more"] = n_groups, int(N - (labels == np.arange(N)).sum())
+            out["device_count"] = int(dc.item())
+            if what == "planted":
+                pairs, _ = ix.duplicates(thr)
+                out["pairs"] = len(pairs)
+            for name, v in ms.items():
+                out[name] = _stats(v, N * E * 4)
+            out["tflops_f32_upper_triangle"] = round(N * (N - 1.0) * E / (out["duplicate_groups_device"]["ms_median"] * 1e-3)
+                                                     / 1e12, 1)
+            print(json.dumps(out), flush=True)
+
+
 def topk_routes_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Qs=(1, 2, 4, 8, 12, 16)):
     """The measurement kNarrowRows (csrc/kernels/kernels.hpp) is set by: for every query count the
     few-query kernel can take, that kernel (route 2) against the wide one (route 1) on an f32 gallery,
@@ -1242,6 +1305,8 @@ if __name__ == "__main__":
         topk_diverse_leg()
     if "topkknn" in which:  # neighbours of stored rows and the k-NN graph against gather + search(k + 1) and the matrix path
         topk_knn_leg()
+    if "topkcomponents" in which:  # duplicate groups (connected components) against the pair list of duplicates
+        topk_components_leg()
     if "kmeans" in which:  # one k-means iteration: assign against the range search, the integer-sum update
         kmeans_leg()
     if "ivf" in which:  # the probed search against the plain search on a clustered gallery
