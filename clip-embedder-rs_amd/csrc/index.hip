@@ -32,6 +32,10 @@
 // rows.  k-means alternates that launch with an integer-sum update and reads one counter back per iteration;
 // its labels, scores, centroids and sums live in buffers of the handle's, lazy like the record buffer.
 //
+// Labelling (clipgpu_index_classify[_device]; kernels/classify.hip).  The assignment's launch with the k best labels
+// of every slot, k <= 16, and their softmax or sigmoid probabilities; the host form's labels share the assignment's
+// centroid buffer and its outputs have a lazy buffer of their own.
+//
 // Inverted lists and the probed search (clipgpu_index_partition, clipgpu_index_search_probed[_device];
 // kernels/lists.hip, kernels/probe.hip).  partition assigns the live rows to the given centroids and sorts their
 // ids by label into CSR lists (device) whose offsets it also keeps on the host; add, add_device, set_rows and
@@ -176,6 +180,8 @@ struct clipgpu_index {
   int64_t kn_work_n = 0;         // lazy, kept likewise
   char* cc_work = nullptr;       // duplicate groups: parent int32 [capacity], the host form's labels int32 [capacity]
                                  // and the counter (CcBuf); lazy, kept likewise
+  char* cf_work = nullptr;       // classify, host form: labels int32, scores, probabilities and (max, sum) rows f32,
+  int64_t cf_work_n = 0;         // cf_work_n entries each (classify_buffers); lazy, grown on demand, kept likewise
   hipStream_t stream = nullptr;  // the host-buffer forms' stream
   hipEvent_t done = nullptr;     // recorded after every device-side operation
 };
@@ -512,6 +518,45 @@ void fetch_assignment(clipgpu_index* ix, const int32_t* d_label, const float* d_
   HIP_CHECK(copy_d2h(l.data(), d_label, l.size() * 4));
   HIP_CHECK(copy_d2h(out_score, d_score, l.size() * 4));
   for (size_t i = 0; i < l.size(); ++i) out_label[i] = l[i];
+}
+
+// ---- labelling every stored row (kernels/classify.hip) ----------------------------------------------------
+static_assert(kClassifyMaxK == CLIPGPU_CLASSIFY_K_MAX, "the header's limit is the kernel's");
+struct ClassifyReq { const float* labels; int64_t C, k; float scale, bias; int probs; const uint32_t* allow; };
+// Device pointers: the caller's for the device form, the regions of cf_work for the host form.
+struct ClassifyBuf { int32_t* label; float* score; float* prob; float* norm; };
+
+// The refusals that need no lock and no device (the activation, NULL arguments, C, then k); then as enter_cluster.
+std::unique_lock<std::mutex> enter_classify(clipgpu_index* ix, const ClassifyReq& r, bool null_out) {
+  if (r.probs == kBadActivation)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "activation must be CLIPGPU_SIM_SOFTMAX or CLIPGPU_SIM_SIGMOID");
+  if (!ix || !r.labels || null_out) throw ClipErr(CLIPGPU_ERR_INVALID, "NULL argument");
+  if (r.C < 1 || r.C > kClusterMaxCentroids)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "the number of labels must be in 1.." + std::to_string(kClusterMaxCentroids) +
+                                           ", got " + std::to_string(r.C));
+  if (r.k < 1 || r.k > kClassifyMaxK)
+    throw ClipErr(CLIPGPU_ERR_INVALID, "k must be in 1.." + std::to_string(kClassifyMaxK) + ", got " +
+                                           std::to_string(r.k));
+  return enter_cluster(ix, false, r.C);
+}
+
+void classify_on(clipgpu_index* ix, const ClassifyReq& r, const float* d_labels, const uint32_t* mask,
+                 const ClassifyBuf& o, hipStream_t s) {
+  HIP_CHECK(launch_classify({ix->gallery, ix->dtype, (int)ix->size, (int)ix->E, d_labels, (int)r.C, (int)r.k, r.scale,
+                             r.bias, r.probs, mask, o.label, o.score, o.prob, o.norm, s}));
+}
+
+// The host form's device outputs for the present rows at depth k.
+ClassifyBuf classify_buffers(clipgpu_index* ix, int64_t k) {
+  const int64_t n = ix->size * std::max<int64_t>(k, 2);  // four regions of n entries: the last holds [size][2]
+  grow(ix->cf_work, ix->cf_work_n, n, 4 * align256((size_t)n * 4));
+  size_t off = 0;
+  ClassifyBuf b;
+  b.label = carve<int32_t>(ix->cf_work, off, (size_t)ix->cf_work_n * 4);
+  b.score = carve<float>(ix->cf_work, off, (size_t)ix->cf_work_n * 4);
+  b.prob = carve<float>(ix->cf_work, off, (size_t)ix->cf_work_n * 4);
+  b.norm = carve<float>(ix->cf_work, off, (size_t)ix->cf_work_n * 4);
+  return b;
 }
 
 
@@ -1668,6 +1713,7 @@ void clipgpu_index_destroy(clipgpu_index* ix) {
   if (ix->dv_work) (void)hipFree(ix->dv_work);
   if (ix->kn_work) (void)hipFree(ix->kn_work);
   if (ix->cc_work) (void)hipFree(ix->cc_work);
+  if (ix->cf_work) (void)hipFree(ix->cf_work);
   if (ix->work) (void)hipFree(ix->work);
   if (ix->gallery) (void)hipFree(ix->gallery);
   delete ix;
@@ -1905,6 +1951,47 @@ int clipgpu_index_assign(clipgpu_index* ix, const float* centroids, int64_t C, f
     mark_last(ix, ix->stream);
     HIP_CHECK(hipStreamSynchronize(ix->stream));
     fetch_assignment(ix, b.label[0], b.score, out_label, out_score);
+  });
+}
+
+int clipgpu_index_classify_device(clipgpu_index* ix, const float* d_labels, int64_t C, int64_t k, float logit_scale,
+                                  float logit_bias, int activation, const uint32_t* d_allow, int32_t* d_label,
+                                  float* d_score, float* d_prob, float* d_norm, void* stream) {
+  return guarded([&]() {
+    const ClassifyReq r = {d_labels, C, k, logit_scale, logit_bias, probs_kind(activation), d_allow};
+    const std::unique_lock<std::mutex> lk = enter_classify(ix, r, !d_label || !d_score || !d_prob);
+    if ((uintptr_t)d_labels & 15) throw ClipErr(CLIPGPU_ERR_INVALID, "d_labels must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    order_after_last(ix, s);
+    classify_on(ix, r, d_labels, build_mask(ix, d_allow, s), {d_label, d_score, d_prob, d_norm}, s);
+    mark_last(ix, s);
+  });
+}
+
+int clipgpu_index_classify(clipgpu_index* ix, const float* labels, int64_t C, int64_t k, float logit_scale,
+                           float logit_bias, int activation, const uint32_t* allow, int64_t* out_label,
+                           float* out_score, float* out_prob, float* out_norm) {
+  return guarded([&]() {
+    const ClassifyReq r = {labels, C, k, logit_scale, logit_bias, probs_kind(activation), allow};
+    const std::unique_lock<std::mutex> lk = enter_classify(ix, r, !out_label || !out_score || !out_prob);
+    HIP_CHECK(hipEventSynchronize(ix->done));  // the filter area and the buffers are free
+    grow(ix->cl_cen, ix->cl_cen_n, C, (size_t)C * ix->E * 4);  // the labels go where assign's centroids go
+    ClassifyBuf b = classify_buffers(ix, k);
+    const bool norm = out_norm && r.probs == TOPK_PROBS_SOFTMAX;  // sigmoid writes none: out_norm stays as it is
+    if (!norm) b.norm = nullptr;
+    if (allow) HIP_CHECK(copy_h2d(ix->d_eff, allow, (size_t)live_words(ix->size) * 4));
+    const uint32_t* mask = build_mask(ix, allow ? ix->d_eff : nullptr, ix->stream);
+    HIP_CHECK(copy_h2d(ix->cl_cen, labels, (size_t)C * ix->E * 4));
+    classify_on(ix, r, (const float*)ix->cl_cen, mask, b, ix->stream);
+    mark_last(ix, ix->stream);
+    HIP_CHECK(hipStreamSynchronize(ix->stream));
+    const size_t n = (size_t)(ix->size * k);
+    std::vector<int32_t> l(n);
+    HIP_CHECK(copy_d2h(l.data(), b.label, n * 4));
+    for (size_t i = 0; i < n; ++i) out_label[i] = l[i];
+    HIP_CHECK(copy_d2h(out_score, b.score, n * 4));
+    HIP_CHECK(copy_d2h(out_prob, b.prob, n * 4));
+    if (norm) HIP_CHECK(copy_d2h(out_norm, b.norm, (size_t)ix->size * 8));
   });
 }
 

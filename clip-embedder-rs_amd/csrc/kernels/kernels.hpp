@@ -558,6 +558,29 @@ struct AssignArgs {
   hipStream_t stream;
 };
 hipError_t launch_assign(const AssignArgs& a);
+
+// Labelling (kernels/classify.hip): launch_assign's scan with the k best labels per gallery row, 1 <= k <=
+// kClassifyMaxK, and their probabilities.  label (int32), score and prob are [N][k], best first: the k largest
+// topk_key(score, label index), (-1, -inf, 0) past min(k, C) and in every slot of a row that mask does not allow.
+// probs: TOPK_PROBS_SOFTMAX (exp(l - M) / S over all C labels; norm [N][2], if given, receives (M, S), (-inf, 0)
+// for a row that is not allowed) or TOPK_PROBS_SIGMOID (similarity.hip's expression; norm unused).  labels: f32
+// [C][E], 16-byte aligned, 1 <= C <= kClusterMaxCentroids.  Nothing at or past row N is written.
+constexpr int kClassifyMaxK = 16;
+struct ClassifyArgs {
+  const void* g;  // [N][E] of dtype (TopkGal)
+  int dtype, N, E;
+  const float* labels;
+  int C, k;
+  float scale, bias;
+  int probs;
+  const uint32_t* mask;
+  int32_t* label;
+  float* score;
+  float* prob;
+  float* norm;
+  hipStream_t stream;
+};
+hipError_t launch_classify(const ClassifyArgs& a);
 // What a k-means call reads back from the device.  The launchers below add to it; the caller zeroes it.
 struct ClusterStat {
   unsigned long long moved;  // launch_cluster_moved: rows with cur[i] >= 0 and cur[i] != prev[i]

@@ -296,6 +296,18 @@ class Clip:
                                                 self._activation())
         return [[(int(i), float(p)) for i, p in zip(ri, rp) if i >= 0] for ri, rp in zip(idx, prob)]
 
+    def classify_index(self, index, labels, k: int = 5, allow=None) -> List[List[Tuple[int, float]]]:
+        """classify (src/clip.rs:92-132) for every image ``index`` stores: per row [(label index, probability)],
+        best first, cut to its k best (k <= 16), with the model's activation (softmax over ALL labels, or
+        sigmoid), logit_scale and logit_bias, as ``classify_topk`` takes them.  ``labels`` is a label index
+        (``build_label_index``; its rows are used as stored, so an f32 one gives ``classify_topk``'s labels) or
+        an array [C, E].  A row that is dead or not allowed by ``allow`` gives an empty list
+        (``EmbeddingIndex.classify``)."""
+        scale, bias = self._scale_bias()
+        rows = labels.rows() if hasattr(labels, "rows") else labels
+        idx, _, prob = index.classify(rows, k, float(scale), float(bias), self._activation(), allow=allow)
+        return [[(int(i), float(p)) for i, p in zip(ri, rp) if i >= 0] for ri, rp in zip(idx, prob)]
+
     @staticmethod
     def softmax(logits) -> np.ndarray:  # src/clip.rs:172-179 (f32, sequential sum; facade.cpp)
         # host-only library (no HIP / RCCL): usable on a host without ROCm

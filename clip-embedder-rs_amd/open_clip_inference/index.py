@@ -19,6 +19,7 @@ COMPOUND_OPS = {"min": 0, "max": 1}  # CLIPGPU_COMPOUND_MIN (all-of), CLIPGPU_CO
 GROUP_MAX = (1 << 31) - 1  # the largest group label of set_groups (include/clipgpu.h)
 RANGE_MAX = 1 << 28  # most records of a range search or a self-join (include/clipgpu.h)
 MAX_CENTROIDS = 1 << 16  # most centroids of assign and kmeans (include/clipgpu.h)
+CLASSIFY_K_MAX = 16  # CLIPGPU_CLASSIFY_K_MAX: the most labels per row of classify
 CODES_MAX_E = 1024  # the widest rows enable_codes takes (include/clipgpu.h)
 DTYPES = {"f32": 0, "f16": 1, "bf16": 2}  # enum clipgpu_index_dtype
 PROB_ACTIVATIONS = {"softmax": 0, "sigmoid": 1}  # CLIPGPU_SIM_SOFTMAX, CLIPGPU_SIM_SIGMOID
@@ -631,6 +632,49 @@ class EmbeddingIndex:
         check(lib().clipgpu_index_assign_device(self.handle, c_void_p(d_centroids), int(C), float(logit_scale),
                                                 float(logit_bias), c_void_p(d_allow or None), c_void_p(d_label),
                                                 c_void_p(d_score), c_void_p(stream or None)))
+
+    def _classify_args(self, k, activation):
+        """(k, the activation's enum) of a ``classify`` call, checked before any native call."""
+        if not 1 <= int(k) <= CLASSIFY_K_MAX:
+            raise ValueError(f"k must be in 1..{CLASSIFY_K_MAX}, got {k}")
+        if activation not in PROB_ACTIVATIONS:
+            raise ValueError(f"activation must be one of {sorted(PROB_ACTIVATIONS)}, got {activation!r}")
+        return int(k), PROB_ACTIVATIONS[activation]
+
+    def classify(self, labels, k: int, logit_scale: float = 1.0, logit_bias: float = 0.0,
+                 activation: str = "softmax", allow=None, return_norm: bool = False):
+        """The k best of ``labels`` [C, E] for every stored row, best first: (labels int64 [len(self), k],
+        logits f32, probs f32).  Row j's entries are what ``search_probs(row j, k)`` of an f32 index holding the
+        labels returns, with ``assign``'s scan: the rows are read as stored, one launch covers the gallery.
+        "softmax": exp(l - M) / sum exp(l_i - M) over ALL C labels; "sigmoid": 1 / (1 + exp(-l)).  Entries past
+        min(k, C) are (-1, -inf, 0), and so is every entry of a row that is dead or not allowed by ``allow`` (as in
+        ``search``).  ``return_norm=True`` adds f32 [len(self), 2], (M, S) per row; NaN for "sigmoid".
+        1 <= C <= 65536, 1 <= k <= 16; k = 1 is ``assign``, bit for bit."""
+        k, act = self._classify_args(k, activation)
+        words = self._allow_words(allow)
+        c = self._centroids(labels, "labels")
+        n = len(self)
+        idx = np.empty((n, k), np.int64)
+        score = np.empty((n, k), np.float32)
+        prob = np.empty((n, k), np.float32)
+        norm = np.full((n, 2), np.nan, np.float32) if return_norm else None
+        check(lib().clipgpu_index_classify(self.handle, c.ctypes.data, c.shape[0], k, float(logit_scale),
+                                           float(logit_bias), act, None if words is None else words.ctypes.data,
+                                           idx.ctypes.data, score.ctypes.data, prob.ctypes.data,
+                                           None if norm is None else norm.ctypes.data))
+        return (idx, score, prob, norm) if return_norm else (idx, score, prob)
+
+    def classify_device(self, d_labels: int, C: int, k: int, d_label: int, d_score: int, d_prob: int,
+                        logit_scale: float = 1.0, logit_bias: float = 0.0, activation: str = "softmax",
+                        stream: int = 0, d_allow: int = 0, d_norm: int = 0) -> None:
+        """``classify`` on device pointers (labels f32 [C, E], 16-byte aligned, in; labels int32, logits and
+        probs f32 [len(self), k] out; ``d_norm`` f32 [len(self), 2] out or 0 = not wanted, written for "softmax"
+        only), ordered on ``stream``; returns without synchronising."""
+        k, act = self._classify_args(k, activation)
+        check(lib().clipgpu_index_classify_device(self.handle, c_void_p(d_labels), int(C), k, float(logit_scale),
+                                                  float(logit_bias), act, c_void_p(d_allow or None),
+                                                  c_void_p(d_label), c_void_p(d_score), c_void_p(d_prob),
+                                                  c_void_p(d_norm or None), c_void_p(stream or None)))
 
     def kmeans(self, n_clusters=None, init=None, max_iter: int = 25, seed: int = 0, allow=None) -> "KMeansResult":
         """Spherical k-means over the live (and allowed) rows: Lloyd iterations of ``assign`` (scale 1, bias

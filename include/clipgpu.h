@@ -775,6 +775,47 @@ int clipgpu_index_components_device(clipgpu_index* ix, float threshold, float lo
                                     const uint32_t* d_allow, int to_groups, int32_t* d_label, uint32_t* d_count,
                                     void* stream);
 
+/* ---- labelling every stored row: the k best labels of each, with probabilities ----------------------------------
+ * Clip::classify (src/clip.rs:92-132) for the pictures the index already holds: clipgpu_index_classify[_device]
+ * give, for every slot j < size, the k best of C label embeddings (f32 [C][E] whatever the gallery's type; the
+ * _device form wants them 16-byte aligned), 1 <= C <= 65536 and 1 <= k <= CLIPGPU_CLASSIFY_K_MAX.  It is
+ * clipgpu_index_assign with a k-deep selection and the probabilities beside it (kernels/classify.hip; DESIGN.md,
+ * embedding index, labelling stored rows); the gallery rows are the queries, read in their storage type.
+ *   label, score [size][k]: the k label indices with the largest topk_key(score, label index), best first --
+ *     exactly what clipgpu_index_search with that k returns for the query g_j (row j as stored, widened exactly)
+ *     from an F32 index holding the C labels: equal scores to the lower label index, a NaN below -inf, (-1, -inf)
+ *     past min(k, C).  score = fmaf(dot(label, g_j), logit_scale, logit_bias) with the bits of
+ *     clipgpu_similarity(labels, rows, logits)[label][j].  k = 1 is clipgpu_index_assign's label and score, bit
+ *     for bit.
+ *   prob [size][k], activation CLIPGPU_SIM_SOFTMAX: exp(l - M_j) / S_j over ALL C labels, not over the k returned,
+ *     M_j the largest logit of row j and S_j = sum exp(l_i - M_j): the reference's classify for image j.  In f32
+ *     with expf; the relative error of a probability and of S_j against exact arithmetic on the same logits is
+ *     bounded in DESIGN.md.  norm [size][2] (NULL = not wanted) receives (M_j, S_j).  A NaN or +inf logit makes the
+ *     row's probabilities NaN, as in clipgpu_index_search_probs.
+ *     CLIPGPU_SIM_SIGMOID: 1 / (1 + expf(-l)), bit-identical to clipgpu_similarity(..., CLIPGPU_SIM_SIGMOID) at
+ *     those entries; norm is left untouched.  Entries past min(k, C) hold probability 0.
+ *   a row that is dead or not allowed (`allow` / `d_allow`: a bitmap over gallery rows, as in the filtered search)
+ *     gets (-1, -inf, 0) in all k slots and norm (-inf, 0).  Nothing at or past `size` is written.
+ *   _device form: d_label int32, d_score, d_prob, d_norm f32; ordered after the handle's last operation on
+ *     `stream`, does not synchronise.  Host form: out_label int64; the labels pass through the buffer of the host
+ *     assign's centroids and the outputs through one of 16 * size * max(k, 2) bytes, which the handle allocates at
+ *     the first such call, grows on demand and keeps until it is destroyed (a failed allocation is
+ *     CLIPGPU_ERR_DEVICE and leaves the index usable).
+ *   One launch covers the gallery, with no span cut and no merge: clipgpu_test_topk_span_cols and
+ *     clipgpu_test_topk_route change nothing.
+ * Refused with CLIPGPU_ERR_INVALID before any device call: a NULL handle, input or required output; C outside
+ * 1 .. 65536; k outside 1 .. CLIPGPU_CLASSIFY_K_MAX; CLIPGPU_SIM_LOGITS or an unknown activation; an empty index
+ * ("Empty batch").
+ * Not offered: k above 16 (the lists live in registers; larger k is the search's business), labels taken from a
+ * second handle without the host hop, a probed form. */
+#define CLIPGPU_CLASSIFY_K_MAX 16
+int clipgpu_index_classify(clipgpu_index* ix, const float* labels, int64_t C, int64_t k, float logit_scale,
+                           float logit_bias, int activation, const uint32_t* allow, int64_t* out_label,
+                           float* out_score, float* out_prob, float* out_norm);
+int clipgpu_index_classify_device(clipgpu_index* ix, const float* d_labels, int64_t C, int64_t k, float logit_scale,
+                                  float logit_bias, int activation, const uint32_t* d_allow, int32_t* d_label,
+                                  float* d_score, float* d_prob, float* d_norm, void* stream);
+
 /* ---- data-parallel sharding + the RCCL all-gather (north_star: "batches shard
  * data-parallel across the 8 GPUs of one node with an RCCL all-gather over xGMI only for the final
  * embedding matrix").  The reference has no multi-device path: embed_images / embed_texts

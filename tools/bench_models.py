@@ -443,6 +443,83 @@ def kmeans_leg(N=1 << 20, E=512, runs=7, warmup=2, Cs=(64, 1024), dtypes=("f32",
                 print(json.dumps(out), flush=True)
 
 
+def topk_classify_leg(N=1 << 20, E=512, runs=7, warmup=2, Cs=(64, 1024, 16384), ks=(1, 5, 16), dtypes=("f32", "f16"),
+                       k_base=5, wall_runs=3, chunk=1 << 16):
+    """Labelling every stored row (clipgpu_index_classify_device, softmax) per label count, depth and storage
+    type, against its floor and against what a caller has without it; the device legs alternate in one process
+    (rotating order, device-event timings after `warmup` rounds):
+      classify_k*  classify_device at k = 1, 5, 16;
+      assign       assign_device on the same data: the same scan with a one-deep selection and no softmax;
+      search       the path without classify, export excluded: search_probs_device at k_base of every gallery row
+                   (widened to f32, already on the device) against an index holding the labels.
+    search_end_to_end_wall_ms is that path as a caller runs it: index.rows() in chunks to the host, then
+    labels.search_probs of each chunk (host clock, the median of `wall_runs`).  classify's labels are checked
+    against assign's at k = 1 and against the search's at k_base (f32: bit for bit with the logits)."""
+    from open_clip_inference import EmbeddingIndex
+    torch.manual_seed(0)
+    s = torch.cuda.current_stream().cuda_stream
+    g = torch.nn.functional.normalize(torch.randn(N, E, device="cuda"), dim=1)
+    for dt in dtypes:
+        esz, tdt = INDEX_DTYPES[dt]
+        gw = g if tdt is None else g.to(tdt).float()  # what the index holds, widened
+        with EmbeddingIndex(E, N, dtype=dt) as ix:
+            ix.add_device(g.data_ptr(), N, s)
+            for C in Cs:
+                lab = torch.nn.functional.normalize(torch.randn(C, E, device="cuda"), dim=1)
+                kmax = max(ks)
+                li = torch.empty((N, kmax), dtype=torch.int32, device="cuda")
+                ls, lp = torch.empty((N, kmax), device="cuda"), torch.empty((N, kmax), device="cuda")
+                al, asc = torch.empty(N, dtype=torch.int32, device="cuda"), torch.empty(N, device="cuda")
+                si = torch.empty((N, k_base), dtype=torch.int64, device="cuda")
+                ss, sp = torch.empty((N, k_base), device="cuda"), torch.empty((N, k_base), device="cuda")
+                with EmbeddingIndex(E, C) as cix:
+                    cix.add_device(lab.data_ptr(), C, s)
+
+                    def classify(k):
+                        ix.classify_device(lab.data_ptr(), C, k, li.data_ptr(), ls.data_ptr(), lp.data_ptr(), 100.0, 0.0,
+                                           "softmax", s)
+
+                    legs = [(f"classify_k{k}", lambda k=k: classify(k)) for k in ks]
+                    legs += [("assign", lambda: ix.assign_device(lab.data_ptr(), C, al.data_ptr(), asc.data_ptr(), 100.0, 0.0, s)),
+                             ("search", lambda: cix.search_probs_device(gw.data_ptr(), N, k_base, si.data_ptr(), ss.data_ptr(),
+                                                                        sp.data_ptr(), 100.0, 0.0, "softmax", s))]
+                    ms = {name: [] for name, _ in legs}
+                    for rnd in range(warmup + runs):
+                        r = rnd % len(legs)
+                        for name, fn in legs[r:] + legs[:r]:  # every leg follows every other equally often
+                            t = _event_ms(fn)
+                            if rnd >= warmup:
+                                ms[name].append(t)
+                    classify(1)
+                    torch.cuda.synchronize()
+                    assert torch.equal(li.view(-1)[:N], al) and torch.equal(ls.view(-1)[:N].view(torch.int32), asc.view(torch.int32))
+                    classify(k_base)
+                    torch.cuda.synchronize()
+                    got = li.view(-1)[:N * k_base].view(N, k_base).long()
+                    assert torch.equal(got, si)
+                    assert torch.equal(ls.view(-1)[:N * k_base].view(torch.int32), ss.view(-1).view(torch.int32))
+                    rel = float(((lp.view(-1)[:N * k_base] - sp.view(-1)).abs() / sp.view(-1).clamp_min(1e-30)).max())
+                    walls = []
+                    for _ in range(wall_runs):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        for first in range(0, N, chunk):
+                            cix.search_probs(ix.rows(first, min(chunk, N - first)), k_base, 100.0, 0.0, "softmax")
+                        walls.append((time.perf_counter() - t0) * 1e3)
+                out = {"measure": "topkclassify", "C": C, "dtype": dt, "N": N, "E": E, "runs": runs, "k_base": k_base,
+                       "same_labels_as_assign_and_search": True, "prob_max_rel_diff_vs_search": rel,
+                       "search_end_to_end_wall_ms": round(float(np.median(walls)), 1),
+                       "search_end_to_end_wall_min_max": [round(min(walls), 1), round(max(walls), 1)]}
+                for name, v in ms.items():
+                    out[name] = _stats(v, N * E * esz)
+                m = {name: out[name]["ms_median"] for name in ms}
+                for k in ks:
+                    out[f"classify_k{k}_over_assign"] = round(m[f"classify_k{k}"] / m["assign"], 3)
+                out["search_over_classify"] = round(m["search"] / m[f"classify_k{k_base}"], 1)
+                out["end_to_end_over_classify"] = round(out["search_end_to_end_wall_ms"] / m[f"classify_k{k_base}"], 1)
+                print(json.dumps(out), flush=True)
+
+
 def ivf_leg(N=1 << 20, E=512, k=10, runs=7, warmup=2, Cs=(256, 1024, 4096), nprobes=(1, 8, 32), Qs=(1, 16, 256),
             dtypes=("f32", "f16"), centres=1024, sigma=0.05):
     """The probed (IVF) search against the plain search, per storage type, list count, query count and nprobe.
@@ -1307,6 +1384,8 @@ if __name__ == "__main__":
         topk_knn_leg()
     if "topkcomponents" in which:  # duplicate groups (connected components) against the pair list of duplicates
         topk_components_leg()
+    if "topkclassify" in which:  # labelling every stored row against assign and against search_probs of the exported rows
+        topk_classify_leg()
     if "kmeans" in which:  # one k-means iteration: assign against the range search, the integer-sum update
         kmeans_leg()
     if "ivf" in which:  # the probed search against the plain search on a clustered gallery
